@@ -8,9 +8,20 @@ dot interaction, BCE, SGD lr 1.0, global batch 2048 (strong scaling over ranks, 
 reference methodology of bench/dlrm_s_benchmark.sh), one lookup per bag (Criteo one-hot).
 
     python bench.py [--gpus N --steps K --warmup W]
+        The plain run: set up, warm up, time K steps, print the result line (the headline
+        fields: metric, value, unit, higher_is_better, dtype, ms_per_step, percentiles).
         N > 1: one process per GPU.  Launched by torch.distributed.run (the driver's form)
         or, when WORLD_SIZE is unset, bench.py starts torch.distributed.run itself (a child
         process, before any GPU call) and returns its exit status.
+    python bench.py --full [...]
+        The plain run, then everything else the line reports: per-kernel-group timing and
+        rooflines, box calibration, the input-pipeline and Zipf-skew rates, the collectives'
+        timing (N > 1) and the CPU baseline (--no-kernel-timing / --no-cpu-baseline leave
+        a part out).
+    python bench.py --dump-outputs DIR [...]
+        After the timed steps, write what the last timed step computed as DIR/<name>.npy
+        (float32; see dump_outputs).  The model, the batches and the step count are fixed
+        by the arguments, so two builds can be compared array for array.
     python bench.py --emulate-world 8 --emulate-rank 2     # one rank of the W=8 job, 1 GPU
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
@@ -661,6 +672,55 @@ def cpu_child(c, seconds: float, cores):
         "ms_per_step": 1000.0 * el / n}), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+DUMP_EMB_ROWS = 16384         # embedding rows per sampled array
+
+
+def dump_outputs(out_dir, tr, last_batch, Bl, B):
+    """--dump-outputs: the state the last timed step left, as ``<name>.npy`` files (float32)
+    (this rank's, on several GPUs).  Call it right after the timed loop, before anything
+    else steps the model.
+
+    * ``prob`` [B_local], ``loss`` [1]: what ``DLRMTrainer.step`` returns for that step;
+    * ``dense_W<i>`` [N, K], ``dense_b<i>`` [N]: every MLP layer after its update (bottom
+      then top);
+    * ``emb_rows_sample`` [n, D]: the rows of the local table store at fixed seeded
+      positions (``emb_rows_sample_index`` holds them as float64: exact below 2^53);
+    * ``emb_rows_last_batch`` [n, D] (plain tables only): the updated rows behind a fixed
+      seeded sample of the last step's lookups (``emb_rows_last_batch_index``: the rows).
+    The tables are sampled, not written whole (27.7 GB at the headline config)."""
+    os.makedirs(out_dir, exist_ok=True)
+    bufs = tr._bufs[(Bl, B)]
+    arrays = {"prob": bufs["prob"], "loss": bufs["loss"]}
+    for i, (W, b) in enumerate(tr.dense_state()):
+        arrays[f"dense_W{i}"] = W
+        arrays[f"dense_b{i}"] = b
+    rng = np.random.RandomState(20240607)
+    n_rows = int(tr.weights.shape[0])
+    if n_rows > 0:
+        pos = np.sort(rng.randint(0, n_rows, size=min(DUMP_EMB_ROWS, n_rows)))
+        arrays["emb_rows_sample_index"] = pos.astype(np.float64)
+        arrays["emb_rows_sample"] = tr.weights[torch.from_numpy(pos).to(tr.dev)]
+        if not tr.qr_active and tr.T_local > 0:
+            n_look = int(last_batch.indices.numel())
+            per_table = n_look // tr.T_local
+            look = torch.from_numpy(np.sort(rng.randint(0, n_look, size=min(DUMP_EMB_ROWS,
+                                                                            n_look)))).to(tr.dev)
+            rows = last_batch.indices[look].long() + tr.row_base.to(tr.dev)[look // per_table]
+            arrays["emb_rows_last_batch_index"] = rows.cpu().numpy().astype(np.float64)
+            arrays["emb_rows_last_batch"] = tr.weights[rows]
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        a = np.ascontiguousarray(a)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError(f"--dump-outputs: {name} would pass {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -692,9 +752,17 @@ def main():
                     "carrying the update's two passes, e.g. 0,2")
     ap.add_argument("--tune", default="", help="A/B: library plan overrides, e.g. "
                     "gemm_tile=64032 (dlrm_set_tuning keys, ops.TUNE_KEYS)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run "
+                    "everything else the line reports: per-kernel-group timing and rooflines, "
+                    "box calibration, input-pipeline and Zipf-skew rates, the collectives' "
+                    "timing (several GPUs) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps "
+                    "write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU "
+                    "baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the "
+                    "per-kernel timing, calibration, input-pipeline and skew runs")
     ap.add_argument("--emulate-world", type=int, default=0, help="one GPU runs rank "
                     "--emulate-rank of a W-rank job: its tables over the global batch, the "
                     "B/W dense batch, collectives replaced by same-size device copies "
@@ -847,14 +915,21 @@ def main():
     elapsed = float(el_t.item())
     value = B * args.steps / elapsed
     loss = float(tr._bufs[(B // world, B)]["loss"].item())
+    Bl = B // world
+    dumped = None
+    if args.dump_outputs and ((rank == 0 and not emulated) or (emulated and local_rank == 0)):
+        # before anything below steps the model again
+        dumped = dump_outputs(args.dump_outputs, tr, batches[(args.steps - 1) % nb], Bl, B)
+
+    # everything past the headline figure runs only under --full
+    kernel_timing = args.full and not args.no_kernel_timing
 
     # ---- per-kernel HIP-event timing pass (same step, eager launches) for the roofline
     roofline, emb_roof, groups, interaction_roof = None, None, None, None
-    Bl = B // world
     # lookups run on the physical tables (a QR table is a quotient + a remainder table)
     flops, fwd_bytes, bwd_bytes = algorithmic_work(c, Bl, B, tr.T_phys, world,
                                                    bottom_fused=tr.bottom_fused)
-    if not args.no_kernel_timing:
+    if kernel_timing:
         # capture one eager step's launches per kernel group (after the timed region: the
         # captured groups run on stale data, which does not change their timing)
         timer = GroupGraphTimer(dev)
@@ -942,30 +1017,31 @@ def main():
                 emb_roof["hbm_fresh_batches"] = {"error": repr(e)}
 
     calib = None
-    if not args.no_kernel_timing:
+    if kernel_timing:
         calib = box_calibration(dev)
     pipe_rate = None
-    if world == 1 and not args.no_kernel_timing:
+    if world == 1 and kernel_timing:
         pipe_rate = input_pipeline_rate(tr, c, B, dev)
     skew = None
-    if world == 1 and not args.no_kernel_timing and not args.no_graph:
+    if world == 1 and kernel_timing and not args.no_graph:
         skew = skew_rate(tr, c, B, uniform_ms=elapsed / args.steps * 1000.0)
 
     comm = None
-    if procs > 1:
+    if procs > 1 and args.full:
         try:
             comm = comm_timing(tr, B // world, B)
         except Exception as e:  # noqa: BLE001 - reported; the headline line must still print
             comm = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not emulated and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not emulated and not args.no_cpu_baseline:
         cpu = cpu_baseline(c, args.cpu_seconds, args.config)
 
     if (rank == 0 and not emulated) or (emulated and local_rank == 0):
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "samples/s", "n_gpus": procs,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
+            "dumped_output_bytes": dumped,
             "ms_per_step": round(elapsed / args.steps * 1000.0, 4),
             "ms_per_step_p10_p50_p90": [pct[10], pct[50], pct[90]],
             "gpu_event_ms_timed_region": round(gpu_event_ms, 4),

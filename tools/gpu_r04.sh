@@ -20,11 +20,11 @@ tests)
   tail -1 "$OUT/smoke.log"
   ;;
 bench)
-  timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+  timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
   tail -c 600 "$OUT/bench.json"
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o kt \
-    -- python3 "$ROOT/bench.py" --no-cpu-baseline --steps 200 --warmup 20 \
+    -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 200 --warmup 20 \
     > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || exit $?
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc \
@@ -35,12 +35,12 @@ bench)
   ;;
 configs)
   for cfg in small kaggle terabyte_qr_rwsadagrad; do
-    timeout -k 10 400 python bench.py --config $cfg > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" \
+    timeout -k 10 400 python bench.py --full --config $cfg > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" \
       || exit $?
     echo "$cfg: $(head -c 200 "$OUT/bench_$cfg.json")"
   done
   # the C3 widths at the W = 8 per-rank batch
-  timeout -k 10 400 python bench.py --batch 256 > "$OUT/bench_b256.json" 2> "$OUT/bench_b256.err" \
+  timeout -k 10 400 python bench.py --full --batch 256 > "$OUT/bench_b256.json" 2> "$OUT/bench_b256.err" \
     || exit $?
   echo "b256: $(head -c 200 "$OUT/bench_b256.json")"
   ;;

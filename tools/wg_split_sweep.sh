@@ -5,7 +5,7 @@ set -o pipefail
 OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out/wgsweep
 mkdir -p "$OUT"
 run() {
-  DLRM_WG_SPLITS="$1" timeout -k 10 120 python bench.py --no-cpu-baseline --steps 200 \
+  DLRM_WG_SPLITS="$1" timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 200 \
     > "$OUT/b.json" 2> "$OUT/b.err" || exit 1
   python -c "import json; d=json.load(open('$OUT/b.json')); print('$1', d['value'], d['kernel_us_per_step']['gemm'])"
 }
