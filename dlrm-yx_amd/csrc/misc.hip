@@ -10,6 +10,7 @@
 //    branch of RWSAdagrad (optim/rwsadagrad.py:117-120) on a flat parameter bucket.
 #include "common.hpp"
 #include "head_roles.hpp"
+#include "head_row.hpp"
 #include "tbe_bwd_roles.hpp"
 
 namespace {
@@ -100,36 +101,8 @@ __global__ __launch_bounds__(256) void head_rows_kernel(int64_t M, int64_t K,
 }
 
 // ---------------------------------------------------------------- fused head --
-// Per-row loss math shared by the head kernels: returns (prob, dz, row loss).
-__device__ __forceinline__ void head_row_math(float z, float t, int loss_kind, float lo,
-                                              float gscale, float invM, float& pc, float& dzv,
-                                              float& l) {
-  const float p = 1.f / (1.f + expf(-z));
-  pc = p;
-  bool pass = true;
-  if (lo > 0.f && lo < 0.5f) {
-    const float hi = 1.f - lo;
-    pass = (p >= lo) && (p <= hi);
-    pc = fminf(fmaxf(p, lo), hi);
-  }
-  float dp;
-  if (loss_kind == DLRM_LOSS_BCE) {
-    const float lp = fmaxf(logf(pc), -100.f);
-    const float l1p = fmaxf(logf(1.f - pc), -100.f);
-    l = -(t * lp + (1.f - t) * l1p);
-    dp = (pc - t) / fmaxf((1.f - pc) * pc, 1e-12f) * invM;
-  } else {
-    const float d = pc - t;
-    l = d * d;
-    dp = 2.f * d * invM;
-  }
-  dp *= gscale;
-  if (!pass) dp = 0.f;
-  dzv = dp * (1.f - p) * p;
-}
-
-constexpr int kHeadRows = 4;  // rows per workgroup (one per wave)
-constexpr int kHeadMaxK = 2048;
+// The per-row math (head_row_dot, head_row_math) and kHeadRows / kHeadMaxK: head_row.hpp,
+// shared with the forward-only head of metrics.hip.
 
 // One pass over the rows of the last layer's input X [M, K] (K includes the folded bias
 // column): z = X w, sigmoid, loss term, dz, the ReLU-masked input gradient
@@ -146,26 +119,16 @@ __global__ __launch_bounds__(256) void head_fused_rows_kernel(
   const int lane = threadIdx.x & 63;
   const float invM = 1.f / (float)M;
   float wr[NC], cp[NC];
+  head_load_w<NC>(w, K, lane, wr);
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int64_t k = lane + 64 * c;
-    wr[c] = k < K ? w[k] : 0.f;
-    cp[c] = 0.f;
-  }
+  for (int c = 0; c < NC; ++c) cp[c] = 0.f;
   const int64_t r0 = (int64_t)blockIdx.x * kHeadRows + wave * (kHeadRows / 4);
   for (int q = 0; q < kHeadRows / 4; ++q) {
     const int64_t m = r0 + q;
     if (m >= M) break;
     const float* xr = X + m * ldx;
     float xv[NC];
-    float sacc = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int64_t k = lane + 64 * c;
-      xv[c] = k < K ? xr[k] : 0.f;
-      sacc = fmaf(xv[c], wr[c], sacc);
-    }
-    sacc = wave_sum(sacc);
+    const float sacc = head_row_dot<NC>(xr, K, lane, wr, xv);
     float pc = 0.f, dzv = 0.f, l = 0.f;
     if (lane == 0) {
       head_row_math(sacc, target ? target[m] : 0.f, loss_kind, lo, gscale, invM, pc, dzv, l);
@@ -541,8 +504,7 @@ int head_step(int64_t M, int64_t K, const float* X, int64_t ldx, float* w, const
   hipLaunchKernelGGL(head_fused_rows_kernel<NC_>, dim3(nblk), dim3(256), 0, st, M, K, X, ldx, w, \
                      target, loss_kind, clamp_lo, grad_scale, prob_out, dz_out, row_loss, dX,  \
                      lddx, relu_mask, part)
-  if (nc <= 2) HR(2); else if (nc <= 4) HR(4); else if (nc <= 5) HR(5); else if (nc <= 8) HR(8);
-  else if (nc <= 12) HR(12); else if (nc <= 17) HR(17); else if (nc <= 24) HR(24); else HR(32);
+  DLRM_HEAD_NC_DISPATCH(nc, HR);
 #undef HR
   DLRM_LAUNCH_CHECK(name);
   if (defer) {  // the finalize pass rides on a later launch (dlrm_gemm_f32_group_role)

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 10
+ABI_VERSION = 11
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -55,6 +55,12 @@ class MlpChain(ctypes.Structure):
 class LaunchRole(ctypes.Structure):
     """struct dlrm_launch_role (include/dlrm_hip.h): a deferred embedding update."""
     _fields_ = [("opaque", ctypes.c_uint64 * 32)]
+
+
+class EvalStateC(ctypes.Structure):
+    """struct dlrm_eval_state (include/dlrm_hip.h): device pointers of an evaluation log."""
+    _fields_ = [("keys", c_void_p), ("capacity", c_int64), ("cursor", c_void_p),
+                ("counts", c_void_p), ("error", c_void_p)]
 
 
 P = c_void_p
@@ -151,6 +157,10 @@ SIGNATURES = {
     "dlrm_csr_from_tables": (c_int32, [c_int32, c_int32, P, P, P, c_int32, P]),
     "dlrm_criteo_decode": (c_int32, [P, c_int64, c_int32, c_int32, c_int64, P, c_int64, P, P,
                                      c_int32, P, c_int32, P]),
+    "dlrm_head_predict": (c_int32, [c_int64, c_int64, P, c_int64, P, c_float, P, P, P, P]),
+    "dlrm_eval_update": (c_int32, [c_int64, P, P, P, P]),
+    "dlrm_eval_metrics_workspace_size": (c_size_t, [c_int64]),
+    "dlrm_eval_metrics": (c_int32, [P, c_int64, P, c_size_t, P, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

@@ -372,6 +372,14 @@ class DLRM_Net(nn.Module):
             if chk is not None:
                 chk.flush()
 
+    @staticmethod
+    def log_eval(state, Z_test, T_test) -> None:
+        """Evaluation (the reference's inference(), dlrm_s_pytorch.py:1071-1091): append this
+        test batch's probabilities and labels to a metrics.EvalState on the device, in place
+        of copying them to the host for sklearn; ``state.compute()`` after the last batch
+        returns the reference's validation_results."""
+        state.update(Z_test.detach(), T_test)
+
     # ----------------------------------------------------------- forward --
     def forward(self, dense_x, lS_o, lS_i):
         if ext_dist.my_size > 1:

@@ -805,6 +805,66 @@ def head_step(X: torch.Tensor, w: torch.Tensor, target: torch.Tensor, loss: str 
     return prob, dz, loss_out
 
 
+def head_predict(X: torch.Tensor, w: torch.Tensor, clamp_lo: float = 0.0,
+                 prob: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+                 state=None) -> torch.Tensor:
+    """Forward-only head (dlrm_head_predict): X [M, K] with the folded bias column, w [K] ->
+    prob [M], bit for bit head_step's prob; w is only read.  With ``target`` and ``state``
+    (a metrics.EvalState) every row is also appended to the state's log and counted."""
+    M, K = X.shape
+    _check_cuda(X, w, prob, target)
+    if prob is None:
+        prob = torch.empty(M, dtype=torch.float32, device=X.device)
+    if (state is None) != (target is None):
+        raise ValueError("head_predict: target and state go together")
+    if target is not None and (target.numel() != M or target.dtype != torch.float32
+                               or not target.is_contiguous()):
+        raise ValueError("head_predict: target must be M contiguous fp32 labels")
+    st = ctypes.byref(state.c_struct()) if state is not None else None
+    _lib.call("dlrm_head_predict", M, K, _p(X), X.stride(0), _p(w), float(clamp_lo), _p(prob),
+              _p(target), st, _stream(X.device))
+    return prob
+
+
+def eval_update(prob: torch.Tensor, target: torch.Tensor, state) -> None:
+    """Append n existing probabilities and their labels to an evaluation state's log and add
+    their confusion counts (dlrm_eval_update); enqueues only, capturable."""
+    _check_cuda(prob, target)
+    prob = prob.reshape(-1)
+    target = target.reshape(-1)
+    if prob.dtype != torch.float32 or target.dtype != torch.float32 or \
+            prob.numel() != target.numel():
+        raise ValueError("eval_update: fp32 prob and target of the same length")
+    prob, target = prob.contiguous(), target.contiguous()
+    _lib.call("dlrm_eval_update", prob.numel(), _p(prob), _p(target),
+              ctypes.byref(state.c_struct()), _stream(prob.device))
+
+
+EVAL_SORT_TILE = 4096  # DLRM_EVAL_SORT_TILE: keys per workgroup tile of the metrics sort
+
+
+def eval_metrics(keys: torch.Tensor, n: Optional[int] = None,
+                 workspace: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sort the first n packed keys (int32 tensor holding the uint32 keys) IN PLACE and
+    reduce their tie groups (dlrm_eval_metrics).  Returns the int64 device tensor
+    [A2, P, N, tie groups, bits of the float64 average-precision sum]."""
+    _check_cuda(keys)
+    if keys.dtype != torch.int32 or not keys.is_contiguous():
+        raise ValueError("eval_metrics: keys must be a contiguous int32 tensor")
+    n = keys.numel() if n is None else int(n)
+    if not 0 <= n <= keys.numel():
+        raise ValueError("eval_metrics: n outside the key buffer")
+    need = _lib.query("dlrm_eval_metrics_workspace_size", n)
+    if workspace is None or workspace.numel() < need:
+        workspace = _ws("eval_metrics", need, keys.device)
+    if out is None:
+        out = torch.empty(5, dtype=torch.int64, device=keys.device)
+    _lib.call("dlrm_eval_metrics", _p(keys), n, _p(workspace), workspace.numel(), _p(out),
+              _stream(keys.device))
+    return out
+
+
 def outer_drelu(dz: torch.Tensor, w: torch.Tensor, X: Optional[torch.Tensor], relu_mask: bool,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     M = dz.shape[0]

@@ -1152,11 +1152,19 @@ class DLRMTrainer:
         all-to-alls, everything on gloo) run eagerly between them.  Run one eager step of
         this batch size first (allocations).  Returns a callable; each call is one full
         training step on the captured buffers."""
+        run, self.capture_mode, self.graphs_per_step = self._capture_segments(
+            lambda: self.segments(batch), pool, whole)
+        return run
+
+    def _capture_segments(self, make_segs, pool, whole):
+        """capture()'s two modes over any segment list (``make_segs()`` builds a fresh one:
+        the training step's or predict_segments').  Returns (callable, mode, graphs per
+        replay)."""
         auto = whole is None
         if auto:
             whole = not self.distributed or bool(getattr(self.comm, "capturable", False))
         if whole:
-            segs = self.segments(batch)
+            segs = make_segs()
             host = [fn for kind, fn in segs if kind == "host"]
             g = torch.cuda.CUDAGraph()
             try:
@@ -1171,23 +1179,20 @@ class DLRMTrainer:
                 warnings.warn(f"whole-step capture with the collectives failed ({e!r}); "
                               "capturing the kernel segments between eager collectives")
                 torch.cuda.synchronize()
-                return self.capture(batch, pool=pool, whole=False)
-            self.capture_mode = "whole"
-            self.graphs_per_step = 1
+                return self._capture_segments(make_segs, pool, False)
 
             def run_whole():
                 g.replay()
                 for fn in host:
                     fn()
-            return run_whole
-        self.capture_mode = "segments"
+            return run_whole, "whole", 1
         in_graph = {"gpu"}
         if getattr(self.comm, "capture_ar", False):
             in_graph.add("ar")
         items = []
         pending = []
-        segs = self.segments(batch)
-        self.graphs_per_step = 0
+        segs = make_segs()
+        graphs = [0]
 
         def flush():
             if not pending:
@@ -1197,7 +1202,7 @@ class DLRMTrainer:
                 launched = [fn() is not _EMPTY for fn in pending]
             if any(launched):  # a segment that enqueued nothing is not replayed
                 items.append(g.replay)
-                self.graphs_per_step += 1
+                graphs[0] += 1
             pending.clear()
 
         for kind, fn in segs:
@@ -1213,7 +1218,159 @@ class DLRMTrainer:
         def run():
             for f in items:
                 f()
+        return run, "segments", graphs[0]
+
+    # ---------------------------------------------------------- evaluation --
+    def predict(self, batch: Batch, metrics=None) -> torch.Tensor:
+        """Forward only: prob [B_local] for ``batch`` (a device tensor owned by this batch
+        size, overwritten by the next predict of it).  Writes no weight, no optimizer
+        state, no gradient and no pending launch role; with ``metrics`` (a
+        metrics.EvalState) the head also logs every (prob, batch.target) sample."""
+        for _kind, fn in self.predict_segments(batch, metrics):
+            fn()
+        return self._predict_bufs(self._buffers(batch.X.shape[0],
+                                                batch.X.shape[0] * self.world))["prob"]
+
+    def _predict_bufs(self, bufs):
+        """The forward-only path's own outputs and GEMM workspaces of a batch size (the
+        activations are the step's scratch; a workspace it might have to grow is not: a
+        captured training graph keeps the addresses of the step's)."""
+        pb = bufs.get("predict")
+        if pb is None:
+            Bl = bufs["prob"].shape[0]
+            pb = bufs["predict"] = {
+                "prob": torch.zeros(Bl, dtype=torch.float32, device=self.dev),
+                "ws": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev),
+                "ws_side": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev)}
+        return pb
+
+    def predict_segments(self, batch: Batch, metrics=None):
+        """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
+        ``segments()``: the lookup (dlrm_tbe_forward; nothing of the backward's sort), the
+        bottom MLP (one GPU: beside the lookup on the side stream when the "fwd" overlap is
+        on; several: beside the all-to-all), the interaction (one GPU, one-hot batches: the
+        gather-fused one, then no lookup launch at all), the top MLP forwards and
+        dlrm_head_predict."""
+        cfg = self.cfg
+        Bl = batch.X.shape[0]
+        B = Bl * self.world
+        n_off = self.T_local * B + 1
+        if self.T_local > 0 and batch.offsets.numel() != n_off:
+            raise ValueError(f"batch offsets hold {batch.offsets.numel()} entries, expected "
+                             f"T_local*B+1 = {n_off} (B = {Bl} x {self.world} ranks)")
+        bufs = self._buffers(Bl, B)
+        pb = self._predict_bufs(bufs)
+        dist = self.distributed
+        c_fwd = self.concurrent and "fwd" in self.overlaps and not dist
+        gather = not dist and self._gather_applies(batch)
+        st = {}
+
+        def gemm(problems, side=False):
+            key = "ws_side" if side else "ws"
+            need = ops.gemm_group_workspace_size(problems)
+            if need > pb[key].numel():  # first use of this batch size (not in capture)
+                pb[key] = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+            ops.gemm_group(problems, pb[key], self.dev)
+
+        def lookup():
+            if self.T_local == 0 or gather:
+                return _EMPTY
+            with record_function("module::forward_pass::embedding_lookup"):
+                idx, off = self._phys_csr(batch, B)
+                out = bufs["P"] if self.qr_active else bufs["E"]
+                ops.tbe_forward(self.weights, self.row_base, self.T_phys, B, idx, off, out=out,
+                                out_batch_stride=out.stride(0), error_flag=self.tbe_error_flag)
+                if self.qr_active:
+                    self._qr_combine(bufs, B)
+
+        def bottom_fwd(side=False):
+            with record_function("module::forward_pass::bottom_mlp"):
+                chain = self._bottom_chain(batch, bufs, sort_wgs=0, standalone=True)
+                if chain is not None:
+                    ops.mlp_chain_forward(chain, self.dev)
+                    return
+                h = batch.X
+                for L, out in zip(self.bot, bufs["bot_act"]):
+                    gemm([self._fwd(L, h, out)], side=side)
+                    h = out
+
+        def fwd_single():
+            s0 = torch.cuda.current_stream(self.dev)
+            if not c_fwd:
+                lookup()
+                bottom_fwd()
+                return
+            self._side.wait_stream(s0)
+            lookup()
+            with torch.cuda.stream(self._side):
+                bottom_fwd(side=True)
+            s0.wait_stream(self._side)
+
+        def top_fwd():
+            x, feats = self._features(bufs, Bl)
+            with record_function("module::forward_pass::interaction"):
+                if gather:
+                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
+                                                cfg.arch_interaction_itself, out=bufs["R"],
+                                                error_flag=self.tbe_error_flag)
+                else:
+                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
+                                         cfg.arch_interaction_itself, out=bufs["R"])
+            h = bufs["R"]
+            with record_function("module::forward_pass::top_mlp"):
+                for L, out in zip(self.top[:-1], bufs["top_act"]):
+                    gemm([self._fwd(L, h, out)])
+                    h = out
+                last = self.top[-1]
+                ops.head_predict(h[:, :last.Kp], last.W[0, :last.Kp], cfg.loss_threshold,
+                                 prob=pb["prob"],
+                                 target=batch.target if metrics is not None else None,
+                                 state=metrics)
+
+        if not dist:
+            return [("gpu", fwd_single), ("gpu", top_fwd)]
+        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
+        return [
+            ("gpu", lookup),
+            ("a2a", a2a_fwd),
+            ("gpu", bottom_fwd),
+            ("a2a", lambda: st.pop("a2a").wait()),
+            ("gpu", top_fwd),
+        ]
+
+    def capture_predict(self, batch: Batch, metrics=None, pool=None):
+        """A replayable forward-only pass for ``batch`` (capture()'s modes over
+        predict_segments).  Run one eager predict of this batch size first (allocations).
+        Each call of the returned callable scores the batch's current contents into the
+        tensor predict() returns; with ``metrics`` every call appends B_local samples (the
+        log's cursor lives on the device)."""
+        run, _mode, _graphs = self._capture_segments(
+            lambda: self.predict_segments(batch, metrics), pool, None)
         return run
+
+    def evaluate(self, batches, metrics) -> dict:
+        """Score every batch into ``metrics`` (a metrics.EvalState, not reset here) and
+        return its compute() dict (on several ranks: over all ranks' samples).  One graph
+        per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
+        batches are copied into.  Index errors are checked once, at the end."""
+        graphs = {}
+        for batch in batches:
+            key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
+                   self._gather_applies(batch))
+            if key not in graphs:
+                fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
+                              batch.target.clone(), batch.max_per_table, batch.one_hot)
+                self.predict(fixed)  # eager, unlogged: allocations
+                torch.cuda.current_stream(self.dev).synchronize()
+                graphs[key] = (fixed, self.capture_predict(fixed, metrics))
+            fixed, run = graphs[key]
+            fixed.X.copy_(batch.X)
+            fixed.offsets.copy_(batch.offsets)
+            fixed.indices.copy_(batch.indices)
+            fixed.target.copy_(batch.target)
+            run()
+        self.check_errors()
+        return metrics.compute(group=self.pg if self.world > 1 else None)
 
     def check_errors(self) -> None:
         """Raise (ops.TBEIndexError / ValueError) if any step since the last check hit an

@@ -113,8 +113,10 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 9: dlrm_adagrad_update_scaled (the W-rank dense Adagrad step with the 1/W folded in)
  *    (round 6).
  * 10: dlrm_tbe_backward_sort + presorted = DLRM_PRESORTED_ANY (the backward's sort run
- *    early, e.g. on a second stream) (round 6). */
-#define DLRM_ABI_VERSION 10 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    early, e.g. on a second stream) (round 6).
+ * 11: evaluation: dlrm_head_predict (the forward-only head), dlrm_eval_state,
+ *    dlrm_eval_update, dlrm_eval_metrics (device ROC-AUC / average precision). */
+#define DLRM_ABI_VERSION 11 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -724,6 +726,64 @@ int dlrm_criteo_decode(const int32_t* records, int64_t n, int32_t n_dense, int32
                        int64_t max_ind_range, float* dense, int64_t ld_dense, float* label,
                        void* indices, int32_t index_bits, void* offsets, int32_t offset_bits,
                        dlrm_stream_t stream);
+
+/* ------------------------------------------------------------- evaluation --- */
+/*
+ * Device evaluation state: a log of one packed key per scored sample plus the running
+ * confusion counts, all in device memory so a captured graph appends at a new position on
+ * every replay.  key = (float_bits(prob) << 1) | label: prob in [0, 1] has a bit pattern
+ * <= 0x3F800000, so unsigned key order is score order with, among equal scores, the
+ * negatives first.  The predicted class is prob > 0.5f (= numpy's round(prob) == 1).
+ * The struct itself lives on the host (device pointers inside); zero *cursor, counts[0..3]
+ * and *error to reset.  (ABI v11)
+ */
+typedef struct dlrm_eval_state {
+  uint32_t* keys;     /* [capacity] key log */
+  int64_t capacity;
+  uint64_t* cursor;   /* number of keys logged so far */
+  uint64_t* counts;   /* [4]: TP, FP, TN, FN */
+  uint32_t* error;    /* dlrm_eval_error bits */
+} dlrm_eval_state;
+
+typedef enum dlrm_eval_error {
+  DLRM_EVAL_ERR_OVERFLOW = 1, /* cursor + rows > capacity: that launch logged nothing */
+  DLRM_EVAL_ERR_SCORE = 2,    /* a prob outside [0, 1] or NaN: its row was skipped */
+  DLRM_EVAL_ERR_LABEL = 4     /* a target that is not exactly 0 or 1: its row was skipped */
+} dlrm_eval_error;
+
+/*
+ * The forward-only head: prob[m] = clamp(sigmoid(X[m] . w)) (bias folded: X carries the
+ * constant-1 column), bit for bit what dlrm_head_step writes for the same X, w and
+ * clamp_lo (the same per-lane fmaf order and wave sum, head_row.hpp); nothing else is
+ * written - no dz, no dX, no partials, no workspace.  K <= 2048.
+ * With target != NULL and state != NULL every row's key is appended at *cursor + m and the
+ * launch's confusion counts are added (integer atomics, one per counter and workgroup);
+ * a one-workgroup follow-up launch then advances *cursor by M, ordered by the stream
+ * after every workgroup's read of it.  Guards: dlrm_eval_error.
+ * Replaces the forward half of the reference's inference() (dlrm_s_pytorch.py:1018-1060).
+ */
+int dlrm_head_predict(int64_t M, int64_t K, const float* X, int64_t ldx, const float* w,
+                      float clamp_lo, float* prob_out, const float* target,
+                      const dlrm_eval_state* state, dlrm_stream_t stream);
+/* The same append and count for n probabilities that already exist (a Z_test tensor). */
+int dlrm_eval_update(int64_t n, const float* prob, const float* target,
+                     const dlrm_eval_state* state, dlrm_stream_t stream);
+
+#define DLRM_EVAL_SORT_TILE 4096 /* keys per workgroup tile of the sort (256 x 16) */
+size_t dlrm_eval_metrics_workspace_size(int64_t n);
+/*
+ * Sorts keys[0, n) IN PLACE (global LSD radix sort, four stable 8-bit passes) and walks
+ * the tie groups (runs of equal key >> 1) of the sorted keys:
+ *   out[0] = A2 = sum_g pos_g (2 neg_below_g + neg_g)   (roc_auc = A2 / (2 P N), exact)
+ *   out[1] = P, out[2] = N, out[3] = number of tie groups
+ *   out[4] = the bits of the double sum_g (pos_g / P) (TP_g / ALL_g)  (average precision;
+ *            TP_g / ALL_g: positives / samples scored >= group g), reduced through
+ *            per-tile partials in fixed order (bitwise reproducible; 0 when P = 0).
+ * out: 5 x uint64 on the device.  n < 2^31.  Replaces sklearn.metrics.roc_auc_score /
+ * average_precision_score of the reference (dlrm_s_pytorch.py:1093-1108).
+ */
+int dlrm_eval_metrics(uint32_t* keys, int64_t n, void* workspace, size_t workspace_bytes,
+                      uint64_t* out, dlrm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,113 @@
+"""CPU checks of the evaluation path: the numpy reference (eval_ref) against sklearn on the
+shared AUC/AP inputs, metrics.finalize on hand-made integers, and the v11 ABI symbols."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import eval_ref
+from conftest import ROOT
+
+from dlrm_hip import _lib, metrics, ops
+
+EVAL_SYMBOLS = ("dlrm_head_predict", "dlrm_eval_update", "dlrm_eval_metrics",
+                "dlrm_eval_metrics_workspace_size")
+CASES = eval_ref.auc_ap_inputs(ops.EVAL_SORT_TILE)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_eval_ref_vs_sklearn(case):
+    import sklearn.metrics as skm
+    name, prob, lab = case
+    got = eval_ref.full(prob, lab)
+    if lab.min() == lab.max():  # n = 1: one class
+        assert name == "n1"
+        try:  # sklearn: ValueError before 1.6, a warning and nan since
+            with pytest.warns(Warning):
+                assert np.isnan(skm.roc_auc_score(lab, prob))
+        except ValueError:
+            pass
+        with pytest.raises(ValueError):
+            metrics.finalize(got["tp"], got["fp"], got["tn"], got["fn"], got["a2"],
+                             got["n_pos"], got["n_neg"], got["ap"])
+        return
+    pred = np.round(prob)
+    tol = 1e-12  # float64 sums of < 2^17 terms bounded by 1
+    assert abs(got["roc_auc"] - skm.roc_auc_score(lab, prob)) <= tol
+    assert abs(got["ap"] - skm.average_precision_score(lab, prob)) <= tol
+    assert abs(got["recall"] - skm.recall_score(lab, pred, zero_division=0)) <= tol
+    assert abs(got["precision"] - skm.precision_score(lab, pred, zero_division=0)) <= tol
+    assert abs(got["f1"] - skm.f1_score(lab, pred, zero_division=0)) <= tol
+    assert abs(got["accuracy"] - skm.accuracy_score(lab, pred)) <= tol
+    fin = metrics.finalize(got["tp"], got["fp"], got["tn"], got["fn"], got["a2"], got["n_pos"],
+                           got["n_neg"], got["ap"])
+    for k in ("recall", "precision", "f1", "ap", "roc_auc", "accuracy"):
+        assert fin[k] == got[k], k
+
+
+def test_equal_scores_give_half():
+    _, prob, lab = [c for c in CASES if c[0] == "equal"][0]
+    got = eval_ref.full(prob, lab)
+    assert got["groups"] == 1
+    assert got["a2"] == got["n_pos"] * got["n_neg"]
+    assert got["roc_auc"] == 0.5
+
+
+def test_finalize_hand_made():
+    # 3 positives, 2 negatives; scores: neg 0.1, pos 0.4, neg 0.6, pos 0.7, pos 0.9
+    # pairs (neg < pos): neg0.1 < 3 pos, neg0.6 < 2 pos -> 5 of 6; A2 = 10
+    r = metrics.finalize(tp=2, fp=1, tn=1, fn=1, auc_num2=10, n_pos=3, n_neg=2, ap=0.8)
+    assert r["roc_auc"] == 10 / 12
+    assert r["recall"] == 2 / 3 and r["precision"] == 2 / 3
+    assert r["f1"] == 4 / 6
+    assert r["accuracy"] == 3 / 5
+    assert r["ap"] == 0.8
+    assert (r["tp"], r["fp"], r["tn"], r["fn"]) == (2, 1, 1, 1)
+    assert (r["auc_num2"], r["n_pos"], r["n_neg"]) == (10, 3, 2)
+    assert set(r) >= {"recall", "precision", "f1", "ap", "roc_auc", "accuracy"}
+
+
+def test_finalize_zero_denominators():
+    # nothing predicted positive: precision 0/0 -> 0.0, recall 0/2, f1 0/2
+    r = metrics.finalize(tp=0, fp=0, tn=3, fn=2, auc_num2=6, n_pos=2, n_neg=3, ap=0.4)
+    assert r["precision"] == 0.0 and r["recall"] == 0.0 and r["f1"] == 0.0
+    assert r["accuracy"] == 3 / 5 and r["roc_auc"] == 0.5
+    # integers beyond 2^53 stay exact up to the final division
+    big = metrics.finalize(tp=1, fp=0, tn=1, fn=0, auc_num2=2 * (2 ** 31 - 1) * 2 ** 31,
+                           n_pos=2 ** 31 - 1, n_neg=2 ** 31, ap=1.0)
+    assert big["roc_auc"] == 1.0
+
+
+@pytest.mark.parametrize("n_pos,n_neg", [(0, 5), (5, 0), (0, 0)])
+def test_finalize_one_class(n_pos, n_neg):
+    with pytest.raises(ValueError):
+        metrics.finalize(tp=0, fp=0, tn=n_neg, fn=n_pos, auc_num2=0, n_pos=n_pos, n_neg=n_neg,
+                         ap=0.0)
+
+
+def test_abi_v11_symbols():
+    with open(os.path.join(ROOT, "include", "dlrm_hip.h")) as f:
+        header = f.read()
+    assert int(re.search(r"#define\s+DLRM_ABI_VERSION\s+(\d+)", header).group(1)) >= 11
+    assert _lib.ABI_VERSION >= 11
+    assert "struct dlrm_eval_state" in header
+    assert int(re.search(r"#define\s+DLRM_EVAL_SORT_TILE\s+(\d+)", header).group(1)) == \
+        ops.EVAL_SORT_TILE
+    for sym in EVAL_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % sym, header), f"{sym} not declared in dlrm_hip.h"
+        assert sym in _lib.SIGNATURES, f"{sym} not bound in _lib.py"
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.fail(f"{_lib.LIB_PATH} is not built")
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for sym in EVAL_SYMBOLS:
+        assert hasattr(lib, sym), f"{sym} not exported by libdlrm_hip.so"
+
+
+def test_package_does_not_import_sklearn():
+    pkg = os.path.join(ROOT, "dlrm-yx_amd", "dlrm_hip")
+    for name in os.listdir(pkg):
+        if name.endswith(".py"):
+            with open(os.path.join(pkg, name)) as f:
+                assert not re.search(r"^\s*(import|from)\s+sklearn", f.read(), re.M), name
