@@ -449,7 +449,9 @@ int dlrm_qr_pool_combine_forward(int32_t op, int32_t T, int64_t B, int64_t D, co
                                  const int32_t* pr, const float* P, int64_t p_batch_stride,
                                  float* E, int64_t e_batch_stride, dlrm_stream_t stream);
 /* dP[b][pq[t]] = dE * P[b][pr[t]], dP[b][pr[t]] = dE * P[b][pq[t]] (mult; add: dE to both);
- * dP[b][pq[t]] = dE for tables without a remainder. */
+ * dP[b][pq[t]] = dE for tables without a remainder.  Gradients are stored, not accumulated:
+ * each physical table belongs to at most one logical one, and dP of a physical table no
+ * logical table names is not written. */
 int dlrm_qr_pool_combine_backward(int32_t op, int32_t T, int64_t B, int64_t D,
                                   const int32_t* pq, const int32_t* pr, const float* P,
                                   int64_t p_batch_stride, const float* dE,

@@ -1545,3 +1545,156 @@ def test_interact_gather_matches_lookup_then_interact(ops, D, F, self_int):
     torch.cuda.synchronize()
     assert int(err.item()) & ops.TBE_ERR_INDEX
     assert torch.equal(R2, ops.interact_forward("dot", x, E2, self_int))
+
+
+# ---------------------------------------------------------------------------------------
+# Direct tests of C-ABI entry points that were reached only through modules (or not at all)
+def _int_tensor(shape, lo, hi, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def _strided(t, fill, pad_rows=2, pad_cols=4):
+    """t as a view of a larger ``fill``-filled device buffer (row stride > row length)."""
+    buf = torch.full((t.shape[0] + pad_rows, t.shape[1] + pad_cols), fill, device=dev)
+    v = buf[:t.shape[0], :t.shape[1]]
+    v.copy_(t)
+    return v, buf
+
+
+def _pads_are(buf, view, fill):
+    r, c = view.shape
+    return bool((buf[:r, c:] == fill).all()) and bool((buf[r:] == fill).all())
+
+
+@pytest.mark.parametrize("op", ["mult", "add", "concat"])
+def test_qr_combine_backward_vs_autograd(ops, op):
+    """dlrm_qr_combine_backward against autograd on the torch expression; integer inputs,
+    so the products are exact and the comparison is bitwise."""
+    n, D = 37, 12
+    eq, er = _int_tensor((n, D), -5, 5, 1), _int_tensor((n, D), -5, 5, 2)
+    go = _int_tensor((n, 2 * D if op == "concat" else D), -5, 5, 3)
+    a, b = eq.clone().requires_grad_(True), er.clone().requires_grad_(True)
+    y = {"mult": lambda: a * b, "add": lambda: a + b, "concat": lambda: torch.cat([a, b], 1)}[op]()
+    (y * go).sum().backward()
+    geq, ger = ops.qr_combine_backward(op, eq.to(dev), er.to(dev), go.to(dev))
+    assert torch.equal(geq.cpu(), a.grad) and torch.equal(ger.cpu(), b.grad)
+
+
+@pytest.mark.parametrize("op", ["mult", "add"])
+def test_qr_pool_combine_forward_backward(ops, op):
+    """dlrm_qr_pool_combine_forward / _backward against the header's formulas, bitwise on
+    integers: 4 logical tables over 6 physical ones (one QR pair, three plain, physical
+    table 4 used by nobody), P / E / dP as views with row strides larger than their rows
+    whose pads stay untouched.  dP of the unused physical table is not written."""
+    B, T, Tp, D = 19, 4, 6, 8
+    pq = torch.tensor([0, 2, 5, 3], dtype=torch.int32, device=dev)
+    pr = torch.tensor([1, -1, -1, -1], dtype=torch.int32, device=dev)
+    P, _ = _strided(_int_tensor((B, Tp * D), -6, 6, 4), float("nan"))
+    dE, _ = _strided(_int_tensor((B, T * D), -6, 6, 5), float("nan"))
+    E, Ebuf = _strided(torch.zeros(B, T * D), -7.0)
+    ops.qr_pool_combine_forward(op, T, B, D, pq, pr, P, E)
+    P3, dE3 = P.reshape(B, Tp, D), dE.reshape(B, T, D)
+    comb = (lambda u, v: u * v) if op == "mult" else (lambda u, v: u + v)
+    refE = torch.stack([comb(P3[:, 0], P3[:, 1]), P3[:, 2], P3[:, 5], P3[:, 3]], 1)
+    assert torch.equal(E.reshape(B, T, D), refE)
+    assert _pads_are(Ebuf, E, -7.0)
+    dP, dPbuf = _strided(torch.full((B, Tp * D), -7.0), -7.0)
+    ops.qr_pool_combine_backward(op, T, B, D, pq, pr, P, dE, dP)
+    ref = torch.full((B, Tp, D), -7.0, device=dev)  # table 4: left as it was
+    ref[:, 0] = dE3[:, 0] * P3[:, 1] if op == "mult" else dE3[:, 0]
+    ref[:, 1] = dE3[:, 0] * P3[:, 0] if op == "mult" else dE3[:, 0]
+    ref[:, 2], ref[:, 5], ref[:, 3] = dE3[:, 1], dE3[:, 2], dE3[:, 3]
+    assert torch.equal(dP.reshape(B, Tp, D), ref)
+    assert _pads_are(dPbuf, dP, -7.0)
+
+
+def test_interact_cat_backward_slices_grad_out(ops):
+    """dlrm_interact_cat_backward: each feature's gradient is its slice of grad_out, bitwise,
+    from a padded grad_out (ld_gout > F * D, NaN pads)."""
+    torch.manual_seed(8)
+    B, F, D = 9, 5, 12
+    x, ly = torch.randn(B, D, device=dev), torch.randn(B, F - 1, D, device=dev)
+    g0 = torch.randn(B, F * D)
+    g, _ = _strided(g0, float("nan"))
+    gx, gly = ops.interact_backward("cat", x, ly, g)
+    assert torch.equal(gx.cpu(), g0[:, :D])
+    assert torch.equal(gly.cpu(), g0[:, D:].reshape(B, F - 1, D))
+    lyl = [ly[:, t].contiguous() for t in range(F - 1)]  # list-of-tensors layout
+    gx2, gl2 = ops.interact_backward("cat", x, lyl, g)
+    assert torch.equal(gx2, gx) and torch.equal(torch.stack(gl2, 1), gly)
+
+
+def test_relu_backward_strided(ops):
+    """dlrm_relu_backward with strided dy / y / dx views, zeros and negatives in y: bitwise
+    dy * (y > 0), the pads of dx untouched."""
+    M, K = 37, 50
+    y0 = _int_tensor((M, K), -2, 2, 6)
+    dy0 = torch.randn(M, K, generator=torch.Generator().manual_seed(7))
+    assert (y0 == 0).any() and (y0 < 0).any()
+    y, _ = _strided(y0, float("nan"), 2, 3)
+    dy, _ = _strided(dy0, float("nan"), 1, 5)
+    dx, dxbuf = _strided(torch.zeros(M, K), -7.0, 2, 1)
+    ops.relu_backward(dy, y, out=dx)
+    assert torch.equal(dx.cpu(), dy0 * (y0 > 0))
+    assert _pads_are(dxbuf, dx, -7.0)
+
+
+def test_sigmoid_forward_backward(ops):
+    """dlrm_sigmoid_forward vs torch.sigmoid of the fp64 input (saturated ends finite and in
+    [0, 1]); dlrm_sigmoid_backward = dy * y * (1 - y); n = 4099 (a ragged tail)."""
+    n = 4099
+    g = torch.Generator().manual_seed(9)
+    x = torch.randn(n, generator=g) * 5
+    x[:9] = torch.tensor([0.0, 1e-8, -1e-8, 20.0, -20.0, 100.0, -100.0, 88.0, -88.0])
+    y = ops.sigmoid_forward(x.to(dev)).cpu()
+    assert torch.isfinite(y).all() and (y >= 0).all() and (y <= 1).all()
+    ok, msg = fp32_close(y.numpy(), torch.sigmoid(x.double()).numpy())
+    assert ok, msg
+    assert y[0] == 0.5 and y[5] == 1.0 and y[6] == 0.0
+    dy = torch.randn(n, generator=g)
+    yy = torch.rand(n, generator=g)
+    yy[:3] = torch.tensor([0.0, 1.0, 0.5])
+    dx = ops.sigmoid_backward(dy.to(dev), yy.to(dev)).cpu()
+    ok, msg = fp32_close(dx.numpy(), (dy.double() * yy.double() * (1 - yy.double())).numpy())
+    assert ok, msg
+    assert dx[0] == 0 and dx[1] == 0
+
+
+@pytest.mark.parametrize("idx_dtype", [torch.int32, torch.int64])
+def test_tbe_psw_grad_direct(ops, idx_dtype):
+    """dlrm_tbe_psw_grad against autograd through embedding_bag(per_sample_weights=...):
+    bag lengths 0..8, one out-of-range index and two lookups after the last bag, which get
+    0 as the header promises."""
+    torch.manual_seed(0)
+    rows, D, B = [300, 7, 50], 32, 24
+    T = len(rows)
+    W = torch.randn(sum(rows), D)
+    lo, li = [], []
+    for n in rows:
+        lens = torch.randint(0, 9, (B,))
+        lo.append(torch.cat([torch.zeros(1, dtype=torch.int64), lens.cumsum(0)[:-1]]))
+        li.append(torch.randint(0, n, (int(lens.sum()),)))
+    off, idx = O.batched_csr(lo, li)
+    n_valid = idx.numel()
+    bad = int(li[0].numel()) + 3  # a lookup of table 1 (7 rows)
+    assert li[1].numel() > 3
+    idx = torch.cat([idx, torch.tensor([1, 2], dtype=idx.dtype)])  # outside every bag
+    idx[bad] = 999
+    G = torch.randn(B, T, D)
+    row_base = torch.tensor([0] + np.cumsum(rows).tolist(), dtype=torch.int64)
+    got = ops.tbe_psw_grad(W.to(dev), row_base.to(dev), T, B, idx.to(idx_dtype).to(dev),
+                           off.to(idx_dtype).to(dev), G.to(dev)).cpu()
+    assert got.shape == (n_valid + 2,)
+    ref = []
+    for t, Wt in enumerate(W.split(rows, 0)):
+        psw = torch.ones(li[t].numel(), dtype=torch.float64, requires_grad=True)
+        y = torch.nn.functional.embedding_bag(li[t], Wt.double(), lo[t], mode="sum",
+                                              per_sample_weights=psw)
+        (y * G[:, t].double()).sum().backward()
+        ref.append(psw.grad)
+    ref = torch.cat(ref + [torch.zeros(2, dtype=torch.float64)])
+    ref[bad] = 0.0
+    ok, msg = fp32_close(got.numpy(), ref.numpy())
+    assert ok, msg
+    assert got[bad] == 0 and got[n_valid] == 0 and got[n_valid + 1] == 0
