@@ -246,6 +246,25 @@ class DLRM_Net(nn.Module):
     def apply_mlp(self, x, layers):
         return layers(x)
 
+    def quantize_mlp(self, bits, dtype="fp16"):
+        """--inference-only --quantize-mlp-with-bit (dlrm_s_pytorch.py:1757-1781).  16: every
+        Linear of bot_l and top_l runs with operands rounded to nearest-even ``dtype`` ("fp16"
+        as the reference, or "bf16") on the 16-bit MFMA, fp32 accumulate, fp32 bias and
+        activation (HipMLP.mlp16); the fp32 parameters stay the only weights, so the
+        state_dict is unchanged and a later load_state_dict takes effect.  fp16 operands above
+        65504 in magnitude become Inf.  32: back to fp32.  Forward under torch.no_grad()
+        only."""
+        if bits == 8:
+            raise NotImplementedError("--quantize-mlp-with-bit 8 (int8 dynamic quantization of "
+                                      "the MLPs) is not implemented; use 16 or 32")
+        if bits not in (16, 32):
+            raise ValueError(f"quantize_mlp: bits {bits!r} (16 or 32)")
+        if dtype not in ops.MLP16_TYPES:
+            raise ValueError(f"quantize_mlp: dtype {dtype!r} (one of {sorted(ops.MLP16_TYPES)})")
+        for mlp in (self.bot_l, self.top_l):
+            mlp.mlp16 = dtype if bits == 16 else None
+        self.quantize_mlp_bits = bits
+
     def quantize_embedding(self, bits):
         """dlrm_s_pytorch.py:609-625: 4- or 8-bit row-wise quantization of every table with
         the reference's own packers (torch.ops.quantized.embedding_bag_{4bit,byte}_prepack,

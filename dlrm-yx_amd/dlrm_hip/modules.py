@@ -384,9 +384,36 @@ class HipPrEmbeddingBag(nn.Module):
 # ------------------------------------------------------------------- MLP ----
 class HipMLP(nn.Sequential):
     """The nn.Sequential[Linear, ReLU|Sigmoid]* built by create_mlp; forward runs all layers
-    through one MLPFunction (state_dict keys unchanged: '0.weight', '0.bias', ...)."""
+    through one MLPFunction (state_dict keys unchanged: '0.weight', '0.bias', ...).
+
+    ``mlp16`` ("bf16" | "fp16", set by DLRM_Net.quantize_mlp; None = fp32): inference only,
+    every Linear as one dlrm_linear16_forward launch - input and weight rounded in flight
+    from the fp32 parameters, fp32 accumulate / bias / ReLU - and the fp32 sigmoid after a
+    sigmoid layer.  No packed weights are kept, so the state_dict is the fp32 one."""
+
+    mlp16 = None
+
+    def _forward16(self, x):
+        if torch.is_grad_enabled():
+            raise RuntimeError("this MLP was quantized for inference (quantize_mlp): run it "
+                               "under torch.no_grad(); like the reference's dynamically "
+                               "quantized model it cannot train")
+        mods = list(self)
+        h = x.detach().to(torch.float32)
+        h = h if h.dim() == 2 and h.stride(-1) == 1 else h.reshape(-1, h.shape[-1]).contiguous()
+        for i, m in enumerate(mods):
+            if isinstance(m, nn.Linear):
+                nxt = mods[i + 1] if i + 1 < len(mods) else None
+                h = ops.linear16_forward(h, m.weight.detach(),
+                                         None if m.bias is None else m.bias.detach(),
+                                         relu=isinstance(nxt, nn.ReLU), dtype=self.mlp16)
+                if isinstance(nxt, nn.Sigmoid):
+                    h = ops.sigmoid_forward(h)
+        return h
 
     def forward(self, x):
+        if self.mlp16 is not None:
+            return self._forward16(x)
         acts, params = [], []
         mods = list(self)
         for i, m in enumerate(mods):

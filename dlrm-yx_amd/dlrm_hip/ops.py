@@ -79,7 +79,7 @@ class DeferredErrorCheck:
 
 # dlrm_tune_key (include/dlrm_hip.h): plan overrides for sweeps and coverage tests
 TUNE_KEYS = {"gemm_tile": 1, "gemm_split": 2, "tbe_block": 3, "tbe_sort": 4, "tbe_lean": 5,
-             "interact_bwd": 6, "interact_fwd": 7}
+             "interact_bwd": 6, "interact_fwd": 7, "linear16_tile": 8}
 
 
 class tuning:
@@ -824,6 +824,50 @@ def head_predict(X: torch.Tensor, w: torch.Tensor, clamp_lo: float = 0.0,
     _lib.call("dlrm_head_predict", M, K, _p(X), X.stride(0), _p(w), float(clamp_lo), _p(prob),
               _p(target), st, _stream(X.device))
     return prob
+
+
+MLP16_TYPES = {"bf16": 0, "fp16": 1}  # dlrm_mlp16_type
+LINEAR16_TILES = (128128, 128064, 64064, 32064)  # DLRM_TUNE_LINEAR16_TILE values
+
+
+def _row_major(t: torch.Tensor, what: str) -> int:
+    """The leading dimension of a 2-D fp32 tensor whose rows are contiguous."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"linear16_forward: {what} must be 2-D fp32 with contiguous rows")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], 1)
+
+
+def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                     relu: bool = False, out: Optional[torch.Tensor] = None,
+                     dtype: str = "bf16") -> torch.Tensor:
+    """Forward-only Linear on the 16-bit MFMA (dlrm_linear16_forward): out [M, N] =
+    act(r16(x) r16(W)^T + bias), x [M, K] and W [N, K] fp32 tensors or views with contiguous
+    rows, each element rounded to nearest-even ``dtype`` ("bf16" | "fp16") in flight, fp32
+    accumulate, fp32 bias / ReLU / output.  ``bias`` may be a strided 1-D view (a column of
+    W's buffer).  Only out[:M, :N] is written (``out`` may be a view of a wider buffer).
+    The library takes 16-byte loads when both base addresses (storage offset included) are
+    16-byte aligned and both row strides are multiples of 4, scalar loads otherwise; neither
+    reads past column K of any row, so the extent of the last row never matters."""
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"linear16_forward: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    _check_cuda(x, W, bias, out)
+    ldx, ldw = _row_major(x, "x"), _row_major(W, "W")
+    (M, K), N = x.shape, W.shape[0]
+    if W.shape[1] != K:
+        raise ValueError(f"linear16_forward: x is [{M}, {K}], W is {list(W.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    ldy = _row_major(out, "out")
+    if tuple(out.shape) != (M, N):
+        raise ValueError(f"linear16_forward: out is {list(out.shape)}, expected [{M}, {N}]")
+    bstride = 0
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != N or bias.dtype != torch.float32:
+            raise ValueError("linear16_forward: bias must be N fp32 values")
+        bstride = bias.stride(0) if N > 1 else 1
+    _lib.call("dlrm_linear16_forward", MLP16_TYPES[dtype], M, N, K, _p(x), ldx, _p(W), ldw,
+              _p(bias), bstride, int(bool(relu)), _p(out), ldy, _stream(x.device))
+    return out
 
 
 def eval_update(prob: torch.Tensor, target: torch.Tensor, state) -> None:

@@ -35,6 +35,9 @@ from . import ops
 from .sharders import shard
 
 
+PRECISIONS = ("fp32", "bf16", "fp16")  # predict / evaluate: the MLP operands' precision
+
+
 def _pad4(n: int) -> int:
     return (int(n) + 3) // 4 * 4
 
@@ -1221,12 +1224,14 @@ class DLRMTrainer:
         return run, "segments", graphs[0]
 
     # ---------------------------------------------------------- evaluation --
-    def predict(self, batch: Batch, metrics=None) -> torch.Tensor:
+    def predict(self, batch: Batch, metrics=None, precision: str = "fp32") -> torch.Tensor:
         """Forward only: prob [B_local] for ``batch`` (a device tensor owned by this batch
         size, overwritten by the next predict of it).  Writes no weight, no optimizer
         state, no gradient and no pending launch role; with ``metrics`` (a
-        metrics.EvalState) the head also logs every (prob, batch.target) sample."""
-        for _kind, fn in self.predict_segments(batch, metrics):
+        metrics.EvalState) the head also logs every (prob, batch.target) sample.
+        ``precision`` "bf16" | "fp16": the MLP layers below the head on the 16-bit MFMA
+        (predict_segments)."""
+        for _kind, fn in self.predict_segments(batch, metrics, precision):
             fn()
         return self._predict_bufs(self._buffers(batch.X.shape[0],
                                                 batch.X.shape[0] * self.world))["prob"]
@@ -1244,13 +1249,25 @@ class DLRMTrainer:
                 "ws_side": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev)}
         return pb
 
-    def predict_segments(self, batch: Batch, metrics=None):
+    def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32"):
         """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
         ``segments()``: the lookup (dlrm_tbe_forward; nothing of the backward's sort), the
         bottom MLP (one GPU: beside the lookup on the side stream when the "fwd" overlap is
         on; several: beside the all-to-all), the interaction (one GPU, one-hot batches: the
         gather-fused one, then no lookup launch at all), the top MLP forwards and
-        dlrm_head_predict."""
+        dlrm_head_predict.
+
+        ``precision`` "bf16" | "fp16" (the reference's --inference-only
+        --quantize-mlp-with-bit 16, dlrm_s_pytorch.py:1757-1781): every bottom- and top-MLP
+        layer except the head runs as one dlrm_linear16_forward launch - input and weight
+        rounded to nearest-even in flight from the fp32 tensors (no weight copy exists),
+        fp32 accumulate, fp32 bias and ReLU, fp32 activations; the fused bottom chain is not
+        used.  The lookup, the interaction, the all-to-all and the head (its K -> 1 layer
+        stays fp32) are the fp32 path's.  Only out[:, :N] of an activation buffer is
+        written, so the constant-1 columns the training step relies on stay."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+        p16 = precision != "fp32"
         cfg = self.cfg
         Bl = batch.X.shape[0]
         B = Bl * self.world
@@ -1283,8 +1300,18 @@ class DLRMTrainer:
                 if self.qr_active:
                     self._qr_combine(bufs, B)
 
+        def linear16(L, h, out):
+            ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True, out=out[:, :L.N],
+                                 dtype=precision)
+
         def bottom_fwd(side=False):
             with record_function("module::forward_pass::bottom_mlp"):
+                if p16:
+                    h = batch.X
+                    for L, out in zip(self.bot, bufs["bot_act"]):
+                        linear16(L, h, out)
+                        h = out
+                    return
                 chain = self._bottom_chain(batch, bufs, sort_wgs=0, standalone=True)
                 if chain is not None:
                     ops.mlp_chain_forward(chain, self.dev)
@@ -1319,7 +1346,10 @@ class DLRMTrainer:
             h = bufs["R"]
             with record_function("module::forward_pass::top_mlp"):
                 for L, out in zip(self.top[:-1], bufs["top_act"]):
-                    gemm([self._fwd(L, h, out)])
+                    if p16:
+                        linear16(L, h, out)
+                    else:
+                        gemm([self._fwd(L, h, out)])
                     h = out
                 last = self.top[-1]
                 ops.head_predict(h[:, :last.Kp], last.W[0, :last.Kp], cfg.loss_threshold,
@@ -1338,31 +1368,36 @@ class DLRMTrainer:
             ("gpu", top_fwd),
         ]
 
-    def capture_predict(self, batch: Batch, metrics=None, pool=None):
+    def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32"):
         """A replayable forward-only pass for ``batch`` (capture()'s modes over
         predict_segments).  Run one eager predict of this batch size first (allocations).
         Each call of the returned callable scores the batch's current contents into the
         tensor predict() returns; with ``metrics`` every call appends B_local samples (the
-        log's cursor lives on the device)."""
+        log's cursor lives on the device).  ``precision``: as predict_segments."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
         run, _mode, _graphs = self._capture_segments(
-            lambda: self.predict_segments(batch, metrics), pool, None)
+            lambda: self.predict_segments(batch, metrics, precision), pool, None)
         return run
 
-    def evaluate(self, batches, metrics) -> dict:
+    def evaluate(self, batches, metrics, precision: str = "fp32") -> dict:
         """Score every batch into ``metrics`` (a metrics.EvalState, not reset here) and
         return its compute() dict (on several ranks: over all ranks' samples).  One graph
         per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
-        batches are copied into.  Index errors are checked once, at the end."""
+        batches are copied into.  Index errors are checked once, at the end.
+        ``precision``: as predict_segments (part of the graph key)."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
-                   self._gather_applies(batch))
+                   self._gather_applies(batch), precision)
             if key not in graphs:
                 fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
                               batch.target.clone(), batch.max_per_table, batch.one_hot)
-                self.predict(fixed)  # eager, unlogged: allocations
+                self.predict(fixed, precision=precision)  # eager, unlogged: allocations
                 torch.cuda.current_stream(self.dev).synchronize()
-                graphs[key] = (fixed, self.capture_predict(fixed, metrics))
+                graphs[key] = (fixed, self.capture_predict(fixed, metrics, precision=precision))
             fixed, run = graphs[key]
             fixed.X.copy_(batch.X)
             fixed.offsets.copy_(batch.offsets)

@@ -115,8 +115,10 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 10: dlrm_tbe_backward_sort + presorted = DLRM_PRESORTED_ANY (the backward's sort run
  *    early, e.g. on a second stream) (round 6).
  * 11: evaluation: dlrm_head_predict (the forward-only head), dlrm_eval_state,
- *    dlrm_eval_update, dlrm_eval_metrics (device ROC-AUC / average precision). */
-#define DLRM_ABI_VERSION 11 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    dlrm_eval_update, dlrm_eval_metrics (device ROC-AUC / average precision).
+ * 12: dlrm_linear16_forward (a forward-only Linear on the 16-bit MFMA: bf16 / fp16 operands
+ *    rounded from the fp32 tensors in flight, fp32 accumulate) + DLRM_TUNE_LINEAR16_TILE. */
+#define DLRM_ABI_VERSION 12 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -142,7 +144,9 @@ const char* dlrm_last_error(void);
  *   DLRM_TUNE_INTERACT_FWD : the dot-interaction forward's kernel: 4 = one wave per sample
  *                          (v4), 5 = one workgroup per sample (v5, D >= 64; default there
  *                          for batches <= 1024)
- *                          (ABI v7) */
+ *                          (ABI v7)
+ *   DLRM_TUNE_LINEAR16_TILE : BM * 1000 + BN of dlrm_linear16_forward's workgroup tile
+ *                          (128128, 128064, 64064, 32064) (ABI v12) */
 enum dlrm_tune_key {
   DLRM_TUNE_GEMM_TILE = 1,
   DLRM_TUNE_GEMM_SPLIT = 2,
@@ -150,7 +154,8 @@ enum dlrm_tune_key {
   DLRM_TUNE_TBE_SORT = 4,
   DLRM_TUNE_TBE_LEAN = 5,
   DLRM_TUNE_INTERACT_BWD = 6,
-  DLRM_TUNE_INTERACT_FWD = 7
+  DLRM_TUNE_INTERACT_FWD = 7,
+  DLRM_TUNE_LINEAR16_TILE = 8
 };
 int dlrm_set_tuning(int32_t key, int64_t value);
 int64_t dlrm_get_tuning(int32_t key);
@@ -786,6 +791,28 @@ size_t dlrm_eval_metrics_workspace_size(int64_t n);
  */
 int dlrm_eval_metrics(uint32_t* keys, int64_t n, void* workspace, size_t workspace_bytes,
                       uint64_t* out, dlrm_stream_t stream);
+
+/* ------------------------------------------------- 16-bit inference Linear -- */
+/*
+ * Forward-only Linear with reduced-precision operands (ABI v12):
+ *   Y[m][n] = act( sum_{k<K} r16(X[m][k]) * r16(W[n][k]) + bias[n * bias_stride] )
+ * X [M][K] (row stride ldx) and W [N][K] (row stride ldw) are fp32 in memory; r16 rounds
+ * each element to nearest-even bf16 or IEEE fp16 inside the kernel (no packed copy of the
+ * weights exists, so none can go stale).  NaN and Inf propagate; an fp16 operand above
+ * 65504 in magnitude becomes Inf - the caller's choice of type.  The products accumulate in
+ * fp32 on v_mfma_f32_16x16x32_{bf16,f16}; the bias add (bias == NULL: none) and the ReLU
+ * (relu != 0) are fp32, Y is fp32.  Only Y[0:M][0:N] is written; no element X[.][k >= K],
+ * W[.][k >= K] or row >= M / >= N is read, whatever the leading dimensions (16-byte loads
+ * are used when X and W are 16-byte aligned and ldx, ldw are multiples of 4, scalar loads
+ * otherwise).  No split-K, no atomics, no workspace: two calls give the same bits.
+ * M == 0 or N == 0: nothing to do.  Replaces the nn.Linear forwards of the reference's
+ * --inference-only --quantize-mlp-with-bit 16 (dlrm_s_pytorch.py:1757-1781).
+ */
+enum dlrm_mlp16_type { DLRM_MLP16_BF16 = 0, DLRM_MLP16_F16 = 1 };
+int dlrm_linear16_forward(int32_t type, int64_t M, int64_t N, int64_t K,
+                          const float* X, int64_t ldx, const float* W, int64_t ldw,
+                          const float* bias, int64_t bias_stride, /* NULL: none */
+                          int32_t relu, float* Y, int64_t ldy, dlrm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,12 +4,15 @@
   * predict: DLRMTrainer.capture_predict at a bench.py config (default terabyte = C3:
     B = 2048, true rows) with an EvalState attached, ms per replay over 10 batches, beside
     the training step's capture() on the same process (bench.py's own figure on the parent
-    commit is the yardstick; this one is for the ratio);
+    commit is the yardstick; this one is for the ratio); with --precision fp32,bf16,fp16 one
+    graph set per precision, timed in alternating windows (fp32, bf16, fp16, fp32, ...,
+    --rounds of them) so the spread between the repeated fp32 windows - the unchanged
+    path - is the yardstick for the 16-bit ones;
   * metrics: dlrm_eval_metrics (sort + tie-group pass) on n random keys beside torch.sort of
     the same keys as int32.
 
 Prints one JSON line.  python tools/eval_bench.py [--config terabyte] [--steps 300]
-[--log2n 24,26] [--skip-predict] [--skip-metrics]
+[--log2n 24,26] [--skip-predict] [--skip-metrics] [--precision fp32,bf16,fp16] [--rounds 3]
 """
 import argparse
 import json
@@ -37,7 +40,7 @@ def _time_ms(fn, steps, warmup):
     return evs[0].elapsed_time(evs[1]) / steps
 
 
-def predict_timing(config, steps, warmup, dev):
+def predict_timing(config, steps, warmup, dev, precisions=("fp32",), rounds=1):
     import bench
     from dlrm_hip import metrics
     from dlrm_hip.trainer import DLRMTrainer, TrainerConfig
@@ -55,14 +58,16 @@ def predict_timing(config, steps, warmup, dev):
     batches = [tr.synthetic_batch(B, c["L"], seed=100 + i) for i in range(nb)]
     for b in batches[:3]:
         tr.step(b)
-        tr.predict(b)
+        for p in precisions:
+            tr.predict(b, precision=p)
     torch.cuda.synchronize()
     st = metrics.EvalState((steps + warmup + 2 * nb) * B, dev)
     pool = torch.cuda.graph_pool_handle()
     train = [tr.capture(b, pool=pool) for b in batches]
-    pred = [tr.capture_predict(b, metrics=st, pool=pool) for b in batches]
+    preds = {p: [tr.capture_predict(b, metrics=st, pool=pool, precision=p) for b in batches]
+             for p in precisions}
     torch.cuda.synchronize()
-    for g in train + pred:  # first (upload) replay of every graph
+    for g in train + [g for p in precisions for g in preds[p]]:  # first (upload) replays
         g()
     torch.cuda.synchronize()
     k = [0]
@@ -75,14 +80,24 @@ def predict_timing(config, steps, warmup, dev):
 
     bench.preheat_device(dev, 300.0)
     train_ms = _time_ms(cycle(train), steps, warmup)
-    st.reset()
-    pred_ms = _time_ms(cycle(pred), steps, warmup)
-    logged = st.count
+    windows = {p: [] for p in precisions}
+    logged = 0
+    for _ in range(rounds):
+        for p in precisions:
+            st.reset()
+            windows[p].append(round(_time_ms(cycle(preds[p]), steps, warmup), 4))
+            logged = st.count
     tr.check_errors()
-    return dict(config=config, batch=B, train_ms_per_step=round(train_ms, 4),
-                predict_ms_per_step=round(pred_ms, 4),
-                predict_over_train=round(pred_ms / train_ms, 3), keys_logged=logged,
-                gather_fused=bool(tr._gather_applies(batches[0])))
+    pred_ms = windows[precisions[0]][0]
+    res = dict(config=config, batch=B, train_ms_per_step=round(train_ms, 4),
+               predict_ms_per_step=pred_ms,
+               predict_over_train=round(pred_ms / train_ms, 3), keys_logged=logged,
+               gather_fused=bool(tr._gather_applies(batches[0])))
+    if len(precisions) > 1 or rounds > 1:
+        res["predict_windows_ms"] = windows
+        res["predict_median_ms"] = {p: sorted(w)[len(w) // 2] for p, w in windows.items()}
+        res["predict_spread_ms"] = {p: round(max(w) - min(w), 4) for p, w in windows.items()}
+    return res
 
 
 def metrics_timing(log2n, dev, reps=5):
@@ -125,7 +140,14 @@ def main():
     ap.add_argument("--log2n", default="24,26")
     ap.add_argument("--skip-predict", action="store_true")
     ap.add_argument("--skip-metrics", action="store_true")
+    ap.add_argument("--precision", default="fp32",
+                    help="comma list of fp32,bf16,fp16: one predict graph set each, timed in "
+                         "alternating windows")
+    ap.add_argument("--rounds", type=int, default=0,
+                    help="windows per precision (default: 3 with several precisions, else 1)")
     args = ap.parse_args()
+    precisions = tuple(p for p in args.precision.split(",") if p)
+    rounds = args.rounds or (3 if len(precisions) > 1 else 1)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     res = {"device": torch.cuda.get_device_name(dev)}
@@ -133,7 +155,8 @@ def main():
         res["metrics"] = [metrics_timing(int(v), dev) for v in args.log2n.split(",") if v]
         torch.cuda.empty_cache()
     if not args.skip_predict:
-        res["predict"] = predict_timing(args.config, args.steps, args.warmup, dev)
+        res["predict"] = predict_timing(args.config, args.steps, args.warmup, dev, precisions,
+                                        rounds)
     print(json.dumps(res))
 
 
