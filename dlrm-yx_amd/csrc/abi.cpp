@@ -7,7 +7,7 @@
 namespace dlrm {
 namespace {
 thread_local char g_last_error[1024] = {0};
-constexpr int kTuneKeys = 9;
+constexpr int kTuneKeys = 12;
 thread_local int64_t g_tuning[kTuneKeys] = {0};
 }
 
@@ -26,7 +26,7 @@ extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }
 extern "C" const char* dlrm_last_error(void) { return dlrm::g_last_error; }
 
 extern "C" int dlrm_set_tuning(int32_t key, int64_t value) {
-  DLRM_ARG(key >= DLRM_TUNE_GEMM_TILE && key <= DLRM_TUNE_LINEAR16_TILE,
+  DLRM_ARG(key >= DLRM_TUNE_GEMM_TILE && key <= DLRM_TUNE_LINEAR16_WGRAD_SPLIT,
            "dlrm_set_tuning: unknown key %d", (int)key);
   DLRM_ARG(value >= 0, "dlrm_set_tuning: negative value");
   dlrm::g_tuning[key] = value;

@@ -13,82 +13,12 @@
 // Neither load path ever reads an element with k >= K or a row >= M / >= N: tail elements
 // are selected to zero (never multiplied), rows past the end are clamped to the last row
 // and their results are not written.  No split-K, no atomics, no workspace.
-#include "common.hpp"
+#include "linear16_stage.hpp"
 
 namespace dlrm {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kBK = 64;        // k elements per step
-constexpr int kThreads = 256;  // 4 waves, 2 (M) x 2 (N)
-
-template <typename T>
-struct Op16;
-template <>
-struct Op16<__bf16> {
-  using vec = bf16x8;
-  static __device__ __forceinline__ f32x4 mfma(vec a, vec b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Op16<_Float16> {
-  using vec = f16x8;
-  static __device__ __forceinline__ f32x4 mfma(vec a, vec b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
-
-// 16-byte chunk index of (row, chunk) in a [rows][8 chunks] LDS tile
-__device__ __forceinline__ int lds_chunk(int row, int c) { return row * 8 + (c ^ ((row >> 1) & 7)); }
-
-// One thread's share of a [ROWS][64] fp32 tile: chunk (tid & 7) of rows (tid >> 3) + 32 i.
-template <int ROWS>
-struct Stage {
-  static constexpr int kIter = ROWS / 32;
-  float v[kIter][8];
-
-  // FULL: the whole k-step lies below K.  ALIGNED: 16-byte loads where the chunk does.
-  template <bool ALIGNED, bool FULL>
-  __device__ __forceinline__ void load(const float* __restrict__ P, int64_t ld, int64_t row0,
-                                       int64_t rows, int64_t k0, int64_t K, int tid) {
-    const int64_t k = k0 + (tid & 7) * 8;
-#pragma unroll
-    for (int i = 0; i < kIter; ++i) {
-      int64_t r = row0 + (tid >> 3) + 32 * i;
-      r = r < rows ? r : rows - 1;  // clamped rows are computed but never written
-      const float* p = P + r * ld + k;
-      if (FULL || k + 8 <= K) {
-        if (ALIGNED) {
-          const float4 a = *reinterpret_cast<const float4*>(p);
-          const float4 b = *reinterpret_cast<const float4*>(p + 4);
-          v[i][0] = a.x, v[i][1] = a.y, v[i][2] = a.z, v[i][3] = a.w;
-          v[i][4] = b.x, v[i][5] = b.y, v[i][6] = b.z, v[i][7] = b.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[i][j] = p[j];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i][j] = (k + j < K) ? p[j] : 0.0f;  // select, not multiply
-      }
-    }
-  }
-
-  template <typename T>
-  __device__ __forceinline__ void store(typename Op16<T>::vec* lds, int tid) const {
-#pragma unroll
-    for (int i = 0; i < kIter; ++i) {
-      typename Op16<T>::vec h;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) h[j] = static_cast<T>(v[i][j]);  // RNE
-      lds[lds_chunk((tid >> 3) + 32 * i, tid & 7)] = h;
-    }
-  }
-};
+using namespace l16;
 
 template <typename T, int BM, int BN, bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void linear16_kernel(
@@ -185,18 +115,13 @@ __global__ __launch_bounds__(kThreads) void linear16_kernel(
   }
 }
 
-struct Tile {
-  int bm, bn;
-};
-constexpr Tile kTiles[] = {{128, 128}, {128, 64}, {64, 64}, {32, 64}};  // largest first
-
 // The largest tile that still gives every CU two workgroups (a workgroup waits on its global
 // loads once per k-step; a second one on the CU fills that time), else the smallest.  At
 // M = 2048: N = 1024 -> 64x64 (512 workgroups), N = 512 -> 32x64 (512), N <= 256 -> 32x64.
 Tile plan_tile(int64_t M, int64_t N, int cus) {
   for (const Tile& t : kTiles)
     if (ceil_div(M, t.bm) * ceil_div(N, t.bn) >= 2 * int64_t(cus)) return t;
-  return kTiles[sizeof(kTiles) / sizeof(kTiles[0]) - 1];
+  return kTiles[kNumTiles - 1];
 }
 
 template <typename T, int BM, int BN>
@@ -230,19 +155,6 @@ bool dispatch(Tile t, bool aligned, int64_t M, int64_t N, int64_t K, const float
   return false;
 }
 
-int device_cus() {
-  static thread_local int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      return 256;
-  }
-  return cus;
-}
-
 }  // namespace
 }  // namespace dlrm
 
@@ -262,9 +174,7 @@ extern "C" int dlrm_linear16_forward(int32_t type, int64_t M, int64_t N, int64_t
   const int64_t forced = tuning(DLRM_TUNE_LINEAR16_TILE);
   Tile t{int(forced / 1000), int(forced % 1000)};
   if (forced != 0) {
-    bool known = false;
-    for (const Tile& c : kTiles) known = known || (c.bm == t.bm && c.bn == t.bn);
-    DLRM_ARG(known, "dlrm_linear16_forward: DLRM_TUNE_LINEAR16_TILE %lld is not a tile",
+    DLRM_ARG(known_tile(t), "dlrm_linear16_forward: DLRM_TUNE_LINEAR16_TILE %lld is not a tile",
              (long long)forced);
   }
   DLRM_REQUIRE(ceil_div(M, 32) * ceil_div(N, 64) <= INT32_MAX, DLRM_ERR_UNSUPPORTED,

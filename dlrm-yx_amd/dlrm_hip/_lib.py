@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 12
+ABI_VERSION = 13
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -163,6 +163,11 @@ SIGNATURES = {
     "dlrm_eval_metrics": (c_int32, [P, c_int64, P, c_size_t, P, P]),
     "dlrm_linear16_forward": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
                                         c_int64, P, c_int64, c_int32, P, c_int64, P]),
+    "dlrm_linear16_dgrad": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
+                                      c_int64, P, c_int64, P, c_int64, P]),
+    "dlrm_linear16_wgrad_workspace_size": (c_size_t, [c_int32, c_int64, c_int64, c_int64]),
+    "dlrm_linear16_wgrad": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
+                                      c_int64, c_int32, c_float, P, c_int64, P, c_size_t, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

@@ -79,7 +79,8 @@ class DeferredErrorCheck:
 
 # dlrm_tune_key (include/dlrm_hip.h): plan overrides for sweeps and coverage tests
 TUNE_KEYS = {"gemm_tile": 1, "gemm_split": 2, "tbe_block": 3, "tbe_sort": 4, "tbe_lean": 5,
-             "interact_bwd": 6, "interact_fwd": 7, "linear16_tile": 8}
+             "interact_bwd": 6, "interact_fwd": 7, "linear16_tile": 8, "linear16_dgrad_tile": 9,
+             "linear16_wgrad_tile": 10, "linear16_wgrad_split": 11}
 
 
 class tuning:
@@ -830,10 +831,10 @@ MLP16_TYPES = {"bf16": 0, "fp16": 1}  # dlrm_mlp16_type
 LINEAR16_TILES = (128128, 128064, 64064, 32064)  # DLRM_TUNE_LINEAR16_TILE values
 
 
-def _row_major(t: torch.Tensor, what: str) -> int:
+def _row_major(t: torch.Tensor, what: str, fn: str = "linear16_forward") -> int:
     """The leading dimension of a 2-D fp32 tensor whose rows are contiguous."""
     if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"linear16_forward: {what} must be 2-D fp32 with contiguous rows")
+        raise ValueError(f"{fn}: {what} must be 2-D fp32 with contiguous rows")
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], 1)
 
 
@@ -867,6 +868,81 @@ def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tens
         bstride = bias.stride(0) if N > 1 else 1
     _lib.call("dlrm_linear16_forward", MLP16_TYPES[dtype], M, N, K, _p(x), ldx, _p(W), ldw,
               _p(bias), bstride, int(bool(relu)), _p(out), ldy, _stream(x.device))
+    return out
+
+
+# DLRM_TUNE_LINEAR16_DGRAD_TILE / DLRM_TUNE_LINEAR16_WGRAD_TILE values
+LINEAR16_DGRAD_TILES = LINEAR16_TILES
+LINEAR16_WGRAD_TILES = LINEAR16_TILES
+WGRAD16_STORE, WGRAD16_SGD = 0, 1  # dlrm_wgrad16_mode
+
+
+def linear16_dgrad(g: torch.Tensor, W: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, dtype: str = "bf16") -> torch.Tensor:
+    """A Linear's data gradient on the 16-bit MFMA (dlrm_linear16_dgrad): out [M, K] =
+    r16(g) r16(W) where ``mask`` > 0 (mask None: everywhere), 0 elsewhere; g [M, N], W [N, K],
+    mask [M, K] fp32 tensors or views with contiguous rows, rounded to nearest-even ``dtype``
+    in flight, fp32 accumulate.  Only out[:M, :K] is written.  Enqueues only; allocates
+    nothing when ``out`` is given."""
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"linear16_dgrad: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    _check_cuda(g, W, mask, out)
+    ldg, ldw = _row_major(g, "g", "linear16_dgrad"), _row_major(W, "W", "linear16_dgrad")
+    (M, N), K = g.shape, W.shape[1]
+    if W.shape[0] != N:
+        raise ValueError(f"linear16_dgrad: g is [{M}, {N}], W is {list(W.shape)}")
+    ldm = 0
+    if mask is not None:
+        ldm = _row_major(mask, "mask", "linear16_dgrad")
+        if tuple(mask.shape) != (M, K):
+            raise ValueError(f"linear16_dgrad: mask is {list(mask.shape)}, expected [{M}, {K}]")
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.float32, device=g.device)
+    ldo = _row_major(out, "out", "linear16_dgrad")
+    if tuple(out.shape) != (M, K):
+        raise ValueError(f"linear16_dgrad: out is {list(out.shape)}, expected [{M}, {K}]")
+    _lib.call("dlrm_linear16_dgrad", MLP16_TYPES[dtype], M, N, K, _p(g), ldg, _p(W), ldw,
+              _p(mask), ldm, _p(out), ldo, _stream(g.device))
+    return out
+
+
+def linear16_wgrad_workspace_size(M: int, N: int, K: int, dtype: str = "bf16") -> int:
+    """Bytes of workspace linear16_wgrad needs for these sizes under the calling thread's
+    tuning overrides (0: none)."""
+    return _lib.query("dlrm_linear16_wgrad_workspace_size", MLP16_TYPES[dtype], M, N, K)
+
+
+def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
+                   lr: Optional[float] = None, dtype: str = "bf16",
+                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A Linear's weight gradient on the 16-bit MFMA (dlrm_linear16_wgrad): acc [N, K] =
+    r16(g)^T r16(x), g [M, N] and x [M, K] fp32 with contiguous rows, rounded to nearest-even
+    ``dtype`` in flight, fp32 accumulate.  ``lr`` None: out = acc; else the fused SGD step
+    out = out - fl(lr * acc).  Only out[:N, :K] is touched.  ``workspace`` (any contiguous
+    tensor of at least linear16_wgrad_workspace_size bytes) holds the partial sums when the
+    planner splits the batch; it is allocated here when needed and not given.  Enqueues only."""
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"linear16_wgrad: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    _check_cuda(g, x, out, workspace)
+    ldg, ldx = _row_major(g, "g", "linear16_wgrad"), _row_major(x, "x", "linear16_wgrad")
+    (M, N), K = g.shape, x.shape[1]
+    if x.shape[0] != M:
+        raise ValueError(f"linear16_wgrad: g is [{M}, {N}], x is {list(x.shape)}")
+    ldc = _row_major(out, "out", "linear16_wgrad")
+    if tuple(out.shape) != (N, K):
+        raise ValueError(f"linear16_wgrad: out is {list(out.shape)}, expected [{N}, {K}]")
+    need = linear16_wgrad_workspace_size(M, N, K, dtype)
+    if workspace is None:
+        if need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    elif not workspace.is_contiguous():
+        raise ValueError("linear16_wgrad: workspace must be contiguous")
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    if ws_bytes < need:
+        raise ValueError(f"linear16_wgrad: workspace of {ws_bytes} bytes, {need} needed")
+    _lib.call("dlrm_linear16_wgrad", MLP16_TYPES[dtype], M, N, K, _p(g), ldg, _p(x), ldx,
+              WGRAD16_STORE if lr is None else WGRAD16_SGD, 0.0 if lr is None else float(lr),
+              _p(out), ldc, _p(workspace), ws_bytes, _stream(g.device))
     return out
 
 

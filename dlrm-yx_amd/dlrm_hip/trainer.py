@@ -20,6 +20,9 @@ optimizer update.  Layout decisions (MI355X-first):
   (rank-major feature order, the W x embedding gradient of the reference is reproduced);
   the bottom MLP overlaps the forward exchange, the backward exchange overlaps the bottom
   MLP backward, and the dense all-reduce overlaps the embedding update.
+* Mixed precision on request (TrainerConfig.mlp_precision = "bf16"): the MLP layers below the
+  head run forward, data gradient and weight gradient on the bf16 MFMA from the same fp32
+  buffers (DLRMTrainer._segments16); everything above stays as described.
 """
 from __future__ import annotations
 
@@ -65,6 +68,19 @@ class TrainerConfig:
     qr_collisions: int = 4
     qr_operation: str = "mult"
     qr_threshold: int = 200
+    # operands of the MLP GEMMs below the head: "fp32", or "bf16" = mixed precision - every
+    # such Linear's forward, data gradient and weight gradient on the 16-bit MFMA with
+    # operands rounded in flight from the fp32 tensors, fp32 accumulation, fp32 master
+    # weights and fp32 everything else (DLRMTrainer._segments16).  "fp16" would need loss
+    # scaling for the gradients: not implemented
+    mlp_precision: str = "fp32"
+
+    def __post_init__(self):
+        if self.mlp_precision == "fp16":
+            raise NotImplementedError("mlp_precision='fp16': fp16 gradients need loss scaling "
+                                      "(predict(..., precision='fp16') is available)")
+        if self.mlp_precision not in ("fp32", "bf16"):
+            raise ValueError(f"mlp_precision {self.mlp_precision!r}: 'fp32' or 'bf16'")
 
 
 @dataclass
@@ -232,6 +248,11 @@ class DLRMTrainer:
         # run the embedding backward's per-table sort inside the lookup launch
         # (dlrm_tbe_forward_presort); False: the backward sorts itself
         self.tbe_presort = True
+        # (cfg.mlp_precision == "bf16", _segments16: a Linear is three 16-bit launches in
+        # stream order and no launch role exists, so group_wgrad, full_last_wgrad, bot_sched,
+        # fuse_bottom, dist_bottom_in_lookup, tbe_role, head_role, tbe_role_at and overlaps
+        # below have no effect in that mode; tbe_presort, early_sort, fuse_gather and
+        # feature_pad keep theirs)
         # MLP backward: a layer's split wgrad (partials only) in the same launch as its dgrad
         self.group_wgrad = True
         self.full_last_wgrad = False
@@ -617,7 +638,11 @@ class DLRMTrainer:
         GEMM launch (the kernel boundary publishes the partials: no reduce launch, no
         in-launch hand-off); the dgrad in that launch reads W_l, never the W_{l+1} the job
         writes.  Optional side-stream overlaps (self.overlaps): "fwd" = bottom MLP || lookup,
-        "bot" = bottom-MLP backward || embedding backward (joined inside the segment)."""
+        "bot" = bottom-MLP backward || embedding backward (joined inside the segment).
+
+        cfg.mlp_precision == "bf16": the list of _segments16 instead."""
+        if self.cfg.mlp_precision != "fp32":
+            return self._segments16(batch, profile)
         cfg = self.cfg
         D = self.D
         Bl = batch.X.shape[0]
@@ -1096,6 +1121,275 @@ class DLRMTrainer:
             ("host", done),
         ]
 
+
+    def _segments16(self, batch: Batch, profile=None):
+        """The mixed-precision step (cfg.mlp_precision == "bf16") in the form of segments().
+
+        Every bottom- and top-MLP Linear below the head is three launches on the 16-bit MFMA,
+        operands rounded to nearest-even from the fp32 tensors in flight, fp32 accumulate:
+          forward  ops.linear16_forward(h[:, :K], W[:, :K], b, ReLU) -> out[:, :N], as
+                   predict_segments issues it (the constant-1 columns stay untouched);
+          backward, layer by layer from the top, in stream order:
+                   ops.linear16_dgrad (mask = the layer's input activation; none for the top
+                   MLP's first layer, no dgrad at all for the bottom MLP's first layer), then
+                   ops.linear16_wgrad over the K + 1 columns [inp | 1] -> [W | b] (the
+                   constant-1 column yields db = sum_m r16(g)), SGD-fused into W on one GPU
+                   with SGD, else stored into the gradient bucket.  Stream order puts a
+                   layer's update after the dgrad that reads its W.
+        The lookup (with its sort role, early_sort, fuse_gather), the interaction, the head
+        (fp32 K -> 1 layer and its gradients), the interaction backward, the embedding
+        backward, the QR combine, the all-to-alls, the all-reduces and the dense update are
+        the fp32 path's calls.  No launch role exists in this mode (self._roles stays empty,
+        the embedding backward and the head run undeferred), the fused bottom chain is not
+        used, and the side stream carries only the early sort: tbe_role, head_role,
+        fuse_bottom, dist_bottom_in_lookup, bot_sched, group_wgrad, full_last_wgrad and
+        overlaps have no effect."""
+        cfg = self.cfg
+        dt = cfg.mlp_precision
+        Bl = batch.X.shape[0]
+        B = Bl * self.world
+        n_off = self.T_local * B + 1
+        if self.T_local > 0 and batch.offsets.numel() != n_off:
+            raise ValueError(f"batch offsets hold {batch.offsets.numel()} entries, expected "
+                             f"T_local*B+1 = {n_off} (B = {Bl} x {self.world} ranks)")
+        bufs = self._buffers(Bl, B)
+        self._cur = bufs
+        prof = profile or (lambda name: _NullCtx())
+        self._prof = prof
+        fused_opt = self.grads is None
+        lr, elr = self.lr, self.emb_lr
+        conc = self.concurrent and profile is None
+        dist = self.distributed
+        st = {}
+        presort = self.tbe_presort
+        gather = presort and not dist and self._gather_applies(batch)
+        self.gather_fused = gather
+        self.bottom_fused = False
+        emb_sizes = "-".join(str(int(cfg.ln_emb[t])) for t in self.local_tables)
+
+        def fwd16(L, h, out):
+            with prof("gemm"):
+                ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True, out=out[:, :L.N],
+                                     dtype=dt)
+
+        def dgrad16(L, g, inp, out):
+            with prof("gemm"):
+                ops.linear16_dgrad(g[:, :L.N], L.W[:, :L.K],
+                                   None if inp is None else inp[:, :L.K], out=out[:, :L.K],
+                                   dtype=dt)
+
+        def wgrad16(L, g, inp):
+            C = L.W if fused_opt else L.gW
+            with prof("gemm"):
+                ops.linear16_wgrad(g[:, :L.N], inp[:, :L.K + 1], C[:, :L.K + 1],
+                                   lr=lr if fused_opt else None, dtype=dt,
+                                   workspace=self._ws_wgrad16(bufs, Bl, L.N, L.K + 1))
+
+        def lookup():
+            self._roles = []
+            with record_function("module::forward_pass::embedding_lookup", emb_sizes), \
+                    prof("tbe_fwd"):
+                if self.T_local == 0:
+                    return
+                if "csr" not in st:
+                    st["csr"] = self._phys_csr(batch, B)
+                idx, off = st["csr"]
+                out = bufs["P"] if self.qr_active else bufs["E"]
+                if presort:
+                    ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B, idx,
+                                            off, self._ws_tbe(idx.numel()),
+                                            batch.max_per_table, out=None if gather else out,
+                                            out_batch_stride=out.stride(0),
+                                            error_flag=self.tbe_error_flag, bottom=None,
+                                            lookup=not gather)
+                else:
+                    ops.tbe_forward(self.weights, self.row_base, self.T_phys, B, idx, off,
+                                    out=out, out_batch_stride=out.stride(0),
+                                    error_flag=self.tbe_error_flag)
+                if self.qr_active:
+                    self._qr_combine(bufs, B)
+
+        def bottom_fwd():
+            h = batch.X
+            with record_function("module::forward_pass::bottom_mlp"):
+                for L, out in zip(self.bot, bufs["bot_act"]):
+                    fwd16(L, h, out)
+                    h = out
+
+        def early_sort():  # the backward's sort on the side stream, beside the forward
+            s0 = torch.cuda.current_stream(self.dev)
+            idx, off = st["csr"] = self._phys_csr(batch, B)
+            self._side.wait_stream(s0)
+            with torch.cuda.stream(self._side), prof("tbe_sort"):
+                ops.tbe_backward_sort(self.weights, self.row_base, self.T_phys, B, idx, off,
+                                      self._ws_tbe(idx.numel()), batch.max_per_table,
+                                      error_flag=self.tbe_error_flag)
+            st["sorted"] = self._side
+
+        def fwd_single():
+            es = (self.early_sort and conc and self.T_local > 0 and presort
+                  and not 0 < batch.max_per_table <= ops.TBE_PRESORT_SEG_CAP)
+            if es and self.early_sort != 2:
+                early_sort()
+            lookup()
+            if es and self.early_sort == 2:
+                early_sort()
+            bottom_fwd()
+
+        def top():  # interaction, top MLP, head, top backward
+            x, feats = self._features(bufs, Bl)
+            with record_function("module::forward_pass::interaction"), prof("interaction_fwd"):
+                if gather:
+                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
+                                                cfg.arch_interaction_itself, out=bufs["R"],
+                                                error_flag=self.tbe_error_flag)
+                else:
+                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
+                                         cfg.arch_interaction_itself, out=bufs["R"])
+            h = bufs["R"]
+            with record_function("module::forward_pass::top_mlp"):
+                for L, out in zip(self.top[:-1], bufs["top_act"]):
+                    fwd16(L, h, out)
+                    h = out
+            last = self.top[-1]
+            G = bufs["g"]
+            gi = 0
+            g = G[gi][:, :last.Kp]
+            with record_function("## Loss Compute ##"), prof("head"):
+                ops.head_step(h[:, :last.Kp], last.W[0, :last.Kp], batch.target,
+                              cfg.loss_function, cfg.loss_threshold, 1.0, prob=bufs["prob"],
+                              dz=bufs["dz"], loss_out=bufs["loss"], dX=g,
+                              relu_mask=len(self.top) > 1,
+                              dw=None if fused_opt else last.gW[0, :last.Kp],
+                              lr=lr if fused_opt else 0.0,
+                              workspace=self._ws_head_step(Bl, last.Kp), defer=False)
+            with record_function("## Backward ##"):
+                for li in range(len(self.top) - 2, -1, -1):
+                    L = self.top[li]
+                    inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
+                    gn = (gi + 1) % 3
+                    dgrad16(L, g, inp if li > 0 else None, G[gn])
+                    wgrad16(L, g, inp)
+                    g, gi = G[gn], gn
+            st.update(x=x, feats=feats, g=g)
+
+        def interaction_bwd():
+            x, feats, g = st.pop("x"), st.pop("feats"), st.pop("g")
+            _, gfeats = self._features(bufs, Bl, grad=True)
+            with record_function("## Backward ##"), prof("interaction_bwd"):
+                if gather:
+                    ops.interact_backward_gather(x, self.weights, self.row_base, batch.indices,
+                                                 g[:, :self.num_int], cfg.arch_interaction_itself,
+                                                 grad_x=bufs["gx"], grad_ly=gfeats, relu_x=True)
+                else:
+                    ops.interact_backward(cfg.arch_interaction_op, x, feats, g[:, :self.num_int],
+                                          cfg.arch_interaction_itself, grad_x=bufs["gx"],
+                                          grad_ly=gfeats, relu_x=True)
+
+        def middle():
+            top()
+            interaction_bwd()
+
+        def bottom_bwd():
+            g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
+            for li in range(self.n_bot - 1, -1, -1):
+                L = self.bot[li]
+                inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
+                if li > 0:
+                    dgrad16(L, g, inp, bufs["gb"][li % 2])
+                wgrad16(L, g, inp)
+                if li > 0:
+                    g = bufs["gb"][li % 2]
+
+        def emb_bwd():
+            with prof("tbe_bwd"):
+                if self.T_local == 0:
+                    return
+                mode = "rowwise_adagrad" if cfg.optimizer == "rwsadagrad" else "sgd"
+                idx, off = st["csr"]
+                grad = bufs["dE"]
+                if self.qr_active:
+                    ops.qr_pool_combine_backward(cfg.qr_operation, self.T_local, B, self.D,
+                                                 self._qr_pq, self._qr_pr, bufs["P"],
+                                                 bufs["dE"], bufs["dP"])
+                    grad = bufs["dP"]
+                s1 = st.pop("sorted", None)
+                if s1 is not None:  # join the early sort
+                    torch.cuda.current_stream(self.dev).wait_stream(s1)
+                ops.tbe_backward(mode, self.weights, self.row_base, self.T_phys, B, idx, off,
+                                 grad, lr=elr, eps=cfg.adagrad_eps, momentum=self.momentum,
+                                 grad_batch_stride=grad.stride(0),
+                                 workspace=self._ws_tbe(idx.numel()),
+                                 max_lookups_per_table=batch.max_per_table,
+                                 error_flag=self.tbe_error_flag,
+                                 presorted=ops.PRESORTED_ANY if s1 is not None else presort)
+
+        @record_function("## Backward ##")
+        def backward_single():
+            bottom_bwd()
+            emb_bwd()
+
+        def dense_update():
+            with record_function("## Backward ##"), prof("dense_update"):
+                scale = 1.0 / self.world
+                if cfg.optimizer == "sgd":
+                    ops.sgd_update(self.params, self.grads, lr * scale)
+                else:
+                    ops.adagrad_update(self.params, self.grads, self.adagrad_sum, lr,
+                                       cfg.adagrad_eps, grad_scale=scale)
+
+        def done():
+            self.step_count += 1
+
+        if not dist:
+            segs = [("gpu", fwd_single), ("gpu", middle), ("gpu", backward_single)]
+            if not fused_opt:
+                segs.append(("gpu", dense_update))
+            return segs + [("host", done)]
+
+        def ar(bucket):
+            def start():
+                g = self.grads[self.n_bot_params:] if bucket == "top" else \
+                    self.grads[:self.n_bot_params]
+                st["ar_" + bucket] = self.comm.allreduce(g)
+            return start
+
+        def wait(key):
+            return lambda: st.pop(key).wait()
+
+        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
+        a2a_bwd = lambda: st.__setitem__("a2a", self._alltoall_bwd(bufs, Bl))  # noqa: E731
+        bwd = lambda fn: record_function("## Backward ##")(fn)  # noqa: E731
+        # the role-free orders of segments(): each captured all-reduce is waited in the graph
+        # that issues it; on other comms the top bucket's all-reduce starts right after the
+        # top backward
+        if getattr(self.comm, "capture_ar", False):
+            return [
+                ("gpu", lookup), ("a2a", a2a_fwd), ("gpu", bottom_fwd), ("a2a", wait("a2a")),
+                ("gpu", top), ("gpu", interaction_bwd), ("a2a", a2a_bwd), ("ar", ar("top")),
+                ("gpu", bwd(bottom_bwd)), ("ar", wait("ar_top")), ("a2a", wait("a2a")),
+                ("ar", ar("bot")), ("gpu", bwd(emb_bwd)), ("ar", wait("ar_bot")),
+                ("gpu", dense_update), ("host", done),
+            ]
+        return [
+            ("gpu", lookup), ("a2a", a2a_fwd), ("gpu", bottom_fwd), ("a2a", wait("a2a")),
+            ("gpu", top), ("ar", ar("top")), ("gpu", interaction_bwd), ("a2a", a2a_bwd),
+            ("gpu", bwd(bottom_bwd)), ("ar", ar("bot")), ("a2a", wait("a2a")),
+            ("gpu", bwd(emb_bwd)), ("ar", wait("ar_top")), ("ar", wait("ar_bot")),
+            ("gpu", dense_update), ("host", done),
+        ]
+
+    def _ws_wgrad16(self, bufs, M: int, N: int, K: int) -> Optional[torch.Tensor]:
+        """The batch size's linear16_wgrad workspace (its layers run in stream order and
+        share it), grown on the eager steps only: a captured graph keeps its address."""
+        need = ops.linear16_wgrad_workspace_size(M, N, K, self.cfg.mlp_precision)
+        ws = bufs.get("wgrad16_ws")
+        if need and (ws is None or ws.numel() < need):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capture() needs one eager step of this batch size first "
+                                   "(the wgrad workspace)")
+            ws = bufs["wgrad16_ws"] = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        return ws
 
     @staticmethod
     def _check_role_at(at):

@@ -117,8 +117,11 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 11: evaluation: dlrm_head_predict (the forward-only head), dlrm_eval_state,
  *    dlrm_eval_update, dlrm_eval_metrics (device ROC-AUC / average precision).
  * 12: dlrm_linear16_forward (a forward-only Linear on the 16-bit MFMA: bf16 / fp16 operands
- *    rounded from the fp32 tensors in flight, fp32 accumulate) + DLRM_TUNE_LINEAR16_TILE. */
-#define DLRM_ABI_VERSION 12 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    rounded from the fp32 tensors in flight, fp32 accumulate) + DLRM_TUNE_LINEAR16_TILE.
+ * 13: dlrm_linear16_dgrad, dlrm_linear16_wgrad (+ _workspace_size): the same Linear's data
+ *    and weight gradients on the 16-bit MFMA, for the mixed-precision training step
+ *    + DLRM_TUNE_LINEAR16_DGRAD_TILE / _WGRAD_TILE / _WGRAD_SPLIT. */
+#define DLRM_ABI_VERSION 13 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -146,7 +149,14 @@ const char* dlrm_last_error(void);
  *                          for batches <= 1024)
  *                          (ABI v7)
  *   DLRM_TUNE_LINEAR16_TILE : BM * 1000 + BN of dlrm_linear16_forward's workgroup tile
- *                          (128128, 128064, 64064, 32064) (ABI v12) */
+ *                          (128128, 128064, 64064, 32064) (ABI v12)
+ *   DLRM_TUNE_LINEAR16_DGRAD_TILE / DLRM_TUNE_LINEAR16_WGRAD_TILE : the same four values
+ *                          for dlrm_linear16_dgrad (tile of dX, M x K) and
+ *                          dlrm_linear16_wgrad (tile of C, N x K) (ABI v13)
+ *   DLRM_TUNE_LINEAR16_WGRAD_SPLIT : workgroups that share one tile's reduction over M in
+ *                          dlrm_linear16_wgrad (1 = no split; clipped to 32 and to the
+ *                          number of 64-row steps); dlrm_linear16_wgrad_workspace_size
+ *                          follows the calling thread's overrides (ABI v13) */
 enum dlrm_tune_key {
   DLRM_TUNE_GEMM_TILE = 1,
   DLRM_TUNE_GEMM_SPLIT = 2,
@@ -155,7 +165,10 @@ enum dlrm_tune_key {
   DLRM_TUNE_TBE_LEAN = 5,
   DLRM_TUNE_INTERACT_BWD = 6,
   DLRM_TUNE_INTERACT_FWD = 7,
-  DLRM_TUNE_LINEAR16_TILE = 8
+  DLRM_TUNE_LINEAR16_TILE = 8,
+  DLRM_TUNE_LINEAR16_DGRAD_TILE = 9,
+  DLRM_TUNE_LINEAR16_WGRAD_TILE = 10,
+  DLRM_TUNE_LINEAR16_WGRAD_SPLIT = 11
 };
 int dlrm_set_tuning(int32_t key, int64_t value);
 int64_t dlrm_get_tuning(int32_t key);
@@ -813,6 +826,47 @@ int dlrm_linear16_forward(int32_t type, int64_t M, int64_t N, int64_t K,
                           const float* X, int64_t ldx, const float* W, int64_t ldw,
                           const float* bias, int64_t bias_stride, /* NULL: none */
                           int32_t relu, float* Y, int64_t ldy, dlrm_stream_t stream);
+
+/* ------------------------------------------------- 16-bit training Linear --- */
+/*
+ * The backward of that Linear with the same conventions (ABI v13): every matrix is fp32 in
+ * memory with contiguous rows and a leading dimension, r16 rounds to nearest-even bf16 /
+ * fp16 (type = dlrm_mlp16_type) inside the kernel, the products accumulate in fp32 on
+ * v_mfma_f32_16x16x32_{bf16,f16}, no packed copy of an operand exists outside the launch,
+ * NaN and Inf propagate, an fp16 operand above 65504 becomes Inf.  No element outside the
+ * stated extents is read or written, whatever the leading dimensions; 16-byte loads are
+ * used when both operands are 16-byte aligned with leading dimensions that are multiples
+ * of 4, element loads otherwise.  No atomics: two calls give the same bits.
+ *
+ * Data gradient:
+ *   dX[m][k] = (mask == NULL || mask[m][k] > 0) ? sum_{n<N} r16(dY[m][n]) * r16(W[n][k]) : 0
+ * dY [M][N], W [N][K], mask [M][K] (the ReLU output the layer's input came from), dX [M][K].
+ * The mask selects (a NaN mask element gives 0, as DLRM_EPI_DRELU's `aux > 0.f ? v : 0.f`);
+ * it never multiplies.  M == 0 or K == 0: nothing to do; N == 0 writes zeros.  Replaces the
+ * autograd backward of nn.Linear + ReLU w.r.t. the input (dlrm_s_pytorch.py:1414).
+ */
+int dlrm_linear16_dgrad(int32_t type, int64_t M, int64_t N, int64_t K,
+                        const float* dY, int64_t lddy, const float* W, int64_t ldw,
+                        const float* mask, int64_t ldmask, /* NULL: none */
+                        float* dX, int64_t lddx, dlrm_stream_t stream);
+/*
+ * Weight gradient, optionally fused with the SGD step:
+ *   acc[n][k] = sum_{m<M} r16(dY[m][n]) * r16(X[m][k]);   dY [M][N], X [M][K], C [N][K]
+ *   DLRM_WGRAD16_STORE: C = acc.   DLRM_WGRAD16_SGD: C = C - fl(lr * acc)  (DLRM_EPI_SGD's
+ *   two roundings).  M == 0: STORE writes zeros, SGD leaves C alone.
+ * The planner may split the reduction over M between workgroups; the partial tiles then go
+ * through `workspace` ([split][N][K] fp32) and a second launch sums them in split order.
+ * dlrm_linear16_wgrad_workspace_size returns the bytes a call with these sizes needs under
+ * the calling thread's tuning overrides (0: none; a larger workspace is fine).  Replaces
+ * the autograd backward of nn.Linear w.r.t. weight and bias (a constant-1 column of X gives
+ * the bias gradient) and optimizer.step() of the reference (dlrm_s_pytorch.py:1414-1421).
+ */
+enum dlrm_wgrad16_mode { DLRM_WGRAD16_STORE = 0, DLRM_WGRAD16_SGD = 1 };
+size_t dlrm_linear16_wgrad_workspace_size(int32_t type, int64_t M, int64_t N, int64_t K);
+int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K,
+                        const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                        int32_t mode, float lr, float* C, int64_t ldc,
+                        void* workspace, size_t workspace_bytes, dlrm_stream_t stream);
 
 #ifdef __cplusplus
 }
