@@ -25,6 +25,19 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace dlrm
 
+// A learning rate that is either a host float baked into the kernel arguments or (ABI v14,
+// the `_dev` entry points) one fp32 in device memory: resolved once at kernel entry, a
+// wave-uniform load.  The pointer comes from the kernel arguments and no kernel that reads a
+// rate writes it (its writer is an earlier kernel or copy, published by the kernel boundary),
+// so the load goes through the constant address space: a scalar load into an SGPR, where the
+// host float already lives - no vector register is spent on it.
+#if defined(__HIPCC__)
+__device__ __forceinline__ float dlrm_resolve_lr(const float* lr_dev, float lr) {
+  typedef const float __attribute__((address_space(4))) * const_f32;
+  return lr_dev ? *(const_f32)lr_dev : lr;
+}
+#endif
+
 #define DLRM_REQUIRE(cond, code, ...)   \
   do {                                  \
     if (!(cond)) {                      \

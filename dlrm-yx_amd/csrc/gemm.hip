@@ -82,6 +82,7 @@ struct GemmParams {
   int* counters;     // per-tile arrival tickets (splits > 1; zero between launches)
   int mode;          // DLRM_GEMM_FULL / _PARTIAL (split partials -> part) / _REDUCE
   float* part;       // PARTIAL/REDUCE: [splits][M][N] fp32, then [splits][M] row sums
+  const float* alpha_dev;  // ABI v14: NULL, or the device fp32 that replaces alpha
 };
 
 struct GemmGroup {
@@ -499,9 +500,10 @@ __device__ __forceinline__ bool splitk_reduce(const GemmParams& p, int tile, int
 // (register r: row 4*(lane>>4) + r, col lane&15 - the same map for every 16x16 MFMA form);
 // rs[i] is the full (this split's) row sum of row wm0 + 16 i + (lane&15) of op(A).
 template <int BM, int BN, int WGM, int WGN, bool RS, int FM, int FN>
-__device__ __forceinline__ void finish_tile(const GemmParams& p, const f32x4 (&acc)[FM][FN],
-                                            float (&rs)[FM], int tile, int split, int tn,
-                                            int64_t m0, int64_t n0, float* smem) {
+__device__ __forceinline__ void finish_tile(const GemmParams& p, float alpha,
+                                            const f32x4 (&acc)[FM][FN], float (&rs)[FM], int tile,
+                                            int split, int tn, int64_t m0, int64_t n0,
+                                            float* smem) {
   constexpr int WM = BM / WGM, WN = BN / WGN;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -588,7 +590,7 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, const f32x4 (&a
           row[q] = (int)(m0 + wm0 + i * 16 + 4 * kq + r);
           col[q] = (int)(n0 + wn0 + j * 16 + l16);
           ok[q] = col[q] < p.N;
-          w[q] = __fmul_rn(p.alpha, v[q]);  // rounded alone, as apply_epilogue sees it
+          w[q] = __fmul_rn(alpha, v[q]);  // rounded alone, as apply_epilogue sees it
         }
     store_elems_any<NV>(p, row, col, ok, w);
     if constexpr (RS) {
@@ -600,7 +602,7 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, const f32x4 (&a
         rrow[i] = (int)(m0 + wm0 + i * 16 + l16);
         rcol[i] = (int)p.ones_col;
         rok[i] = rs_owner;
-        rw[i] = __fmul_rn(p.alpha, rs[i]);
+        rw[i] = __fmul_rn(alpha, rs[i]);
       }
       store_elems_any<FM>(p, rrow, rcol, rok, rw);
     }
@@ -614,14 +616,14 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, const f32x4 (&a
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = m0 + wm0 + i * 16 + 4 * kq + r;
-        if (row < p.M && col < p.N) apply_epilogue(p, row, col, p.alpha * v[(i * FN + j) * 4 + r]);
+        if (row < p.M && col < p.N) apply_epilogue(p, row, col, alpha * v[(i * FN + j) * 4 + r]);
       }
     }
   if (rs_owner) {
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
       const int64_t row = m0 + wm0 + i * 16 + l16;
-      if (row < p.M) apply_epilogue(p, row, p.ones_col, p.alpha * rs[i]);
+      if (row < p.M) apply_epilogue(p, row, p.ones_col, alpha * rs[i]);
     }
   }
 }
@@ -648,6 +650,9 @@ __device__ __forceinline__ void pipe_body(const GemmParams& p, int lb, float* sm
   constexpr int NS = SA::NV + SB::NV;  // staged float4 per thread per stage
   static_assert(NS <= U * KL - 1, "staging must finish before the barrier step");
 
+  // the epilogue's scale: the host float, or (ABI v14) one fp32 of device memory read here,
+  // at entry (a scalar load the K loop hides)
+  const float alpha = dlrm_resolve_lr(p.alpha_dev, p.alpha);
   const int tile = lb / p.splits;
   const int split = lb - tile * p.splits;
   // Grouped raster: runs of kRasterRows tile rows are walked column by column, so the
@@ -851,7 +856,7 @@ __device__ __forceinline__ void pipe_body(const GemmParams& p, int lb, float* sm
     rs[i] += __shfl_xor(rs[i], 32, 64);
   }
   DLRM_GEMM_STAMP(-2);
-  finish_tile<BM, BN, WGM, WGN, RS>(p, acc, rs, tile, split, tn, m0, n0, smem);
+  finish_tile<BM, BN, WGM, WGN, RS>(p, alpha, acc, rs, tile, split, tn, m0, n0, smem);
   DLRM_GEMM_STAMP(-1);
 }
 
@@ -859,6 +864,7 @@ __device__ __forceinline__ void pipe_body(const GemmParams& p, int lb, float* sm
 // in-launch reduction), one float4 of the [M][N] slab per thread, then one row sum per
 // thread for ones_col.  Up to 8 splits' loads in flight.
 __device__ __forceinline__ void reduce_body(const GemmParams& p, int lb) {
+  const float alpha = dlrm_resolve_lr(p.alpha_dev, p.alpha);
   const int64_t MN = p.M * p.N;
   const int64_t i = (int64_t)lb * blockDim.x + threadIdx.x;
   const int64_t n4 = MN / 4;  // N % 4 == 0 (host check)
@@ -889,24 +895,24 @@ __device__ __forceinline__ void reduce_body(const GemmParams& p, int lb) {
       const bool sgd = p.epi == DLRM_EPI_SGD;
       // alpha * acc rounded on its own (no contraction into the add): apply_epilogue's
       // arithmetic, bitwise
-      const float v0 = __fmul_rn(p.alpha, acc.x), v1 = __fmul_rn(p.alpha, acc.y);
-      const float v2 = __fmul_rn(p.alpha, acc.z), v3 = __fmul_rn(p.alpha, acc.w);
+      const float v0 = __fmul_rn(alpha, acc.x), v1 = __fmul_rn(alpha, acc.y);
+      const float v2 = __fmul_rn(alpha, acc.z), v3 = __fmul_rn(alpha, acc.w);
       cp[0] = sgd ? o0 - v0 : o0 + v0;
       cp[1] = sgd ? o1 - v1 : o1 + v1;
       cp[2] = sgd ? o2 - v2 : o2 + v2;
       cp[3] = sgd ? o3 - v3 : o3 + v3;
       return;
     }
-    apply_epilogue(p, row, col, p.alpha * acc.x);
-    apply_epilogue(p, row, col + 1, p.alpha * acc.y);
-    apply_epilogue(p, row, col + 2, p.alpha * acc.z);
-    apply_epilogue(p, row, col + 3, p.alpha * acc.w);
+    apply_epilogue(p, row, col, alpha * acc.x);
+    apply_epilogue(p, row, col + 1, alpha * acc.y);
+    apply_epilogue(p, row, col + 2, alpha * acc.z);
+    apply_epilogue(p, row, col + 3, alpha * acc.w);
   } else if (p.ones_col >= 0 && i - n4 < p.M) {
     const int64_t row = i - n4;
     const float* rsrc = p.part + (int64_t)S * MN + row;
     float acc = rsrc[0];
     for (int s = 1; s < S; ++s) acc += rsrc[(int64_t)s * p.M];
-    apply_epilogue(p, row, p.ones_col, p.alpha * acc);
+    apply_epilogue(p, row, p.ones_col, alpha * acc);
   }
 }
 
@@ -984,6 +990,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_generic_kernel(const GemmPar
   float* Bs0 = smem + SA::SIZE;
   float* As1 = smem + SA::SIZE + SB::SIZE;
   float* Bs1 = As1 + SA::SIZE;
+  const float alpha = dlrm_resolve_lr(p.alpha_dev, p.alpha);
   const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   const int tm = tile / p.tiles_n, tn = tile - (tile / p.tiles_n) * p.tiles_n;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
@@ -1034,7 +1041,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_generic_kernel(const GemmPar
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t row = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (row < p.M && col < p.N) apply_epilogue(p, row, col, p.alpha * acc[r]);
+    if (row < p.M && col < p.N) apply_epilogue(p, row, col, alpha * acc[r]);
   }
 }
 
@@ -1042,6 +1049,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_generic_kernel(const GemmPar
 // epi(alpha * sum_k op(A)(m, k)); 64 rows x 4 k-slices per block, slices added in order.
 __global__ __launch_bounds__(kThreads) void gemm_rowsum_kernel(const GemmParams p, bool a_kc) {
   __shared__ float part[4][64];
+  const float alpha = dlrm_resolve_lr(p.alpha_dev, p.alpha);
   const int tid = threadIdx.x, r = tid & 63, ks = tid >> 6;
   const int64_t m = (int64_t)blockIdx.x * 64 + r;
   float s = 0.f;
@@ -1050,7 +1058,7 @@ __global__ __launch_bounds__(kThreads) void gemm_rowsum_kernel(const GemmParams 
   part[ks][r] = s;
   __syncthreads();
   if (ks == 0 && m < p.M)
-    apply_epilogue(p, m, p.ones_col, p.alpha * (((part[0][r] + part[1][r]) + part[2][r]) + part[3][r]));
+    apply_epilogue(p, m, p.ones_col, alpha * (((part[0][r] + part[1][r]) + part[2][r]) + part[3][r]));
 }
 
 // ------------------------------------------------------------------- planning --
@@ -1088,6 +1096,7 @@ struct Desc {  // one problem as the host sees it
   int32_t mode = DLRM_GEMM_FULL;
   int32_t splits = 0;
   float* part = nullptr;
+  const float* alpha_dev = nullptr;
 };
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1247,6 +1256,7 @@ int launch_group(int n, const Desc* d, const Plan* pl, void* ws, size_t ws_bytes
     p.layout = layout_of(d[i]);
     p.mode = d[i].mode;
     p.part = d[i].part;
+    p.alpha_dev = d[i].alpha_dev;
     p.tiles_m = (int)dlrm::ceil_div(p.M, BM);
     p.tiles_n = (int)dlrm::ceil_div(p.N, BN);
     p.splits = pl[i].splits;
@@ -1315,6 +1325,7 @@ int launch_generic(const Desc& d, hipStream_t st) {
   p.A = d.A, p.lda = d.lda, p.B = d.B, p.ldb = d.ldb;
   p.C = d.C, p.ldc = d.ldc, p.epi = d.epi, p.bias = d.bias;
   p.aux = d.aux, p.ldaux = d.ldaux, p.ones_col = d.ones_col;
+  p.alpha_dev = d.alpha_dev;
   p.tiles_m = (int)dlrm::ceil_div(p.M, 64);
   p.tiles_n = (int)dlrm::ceil_div(p.N, 64);
   p.splits = 1;
@@ -1449,6 +1460,7 @@ Desc desc_of(const dlrm_gemm_problem& g) {
   d.C = g.C, d.ldc = g.ldc, d.epi = g.epilogue, d.bias = g.bias;
   d.aux = g.aux, d.ldaux = g.ld_aux, d.ones_col = g.ones_col;
   d.mode = g.mode, d.splits = g.splits, d.part = g.partial;
+  d.alpha_dev = g.alpha_dev;
   return d;
 }
 

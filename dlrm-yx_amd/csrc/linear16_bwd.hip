@@ -101,6 +101,7 @@ struct BwdArgs {
   int64_t ldo;
   int epi;
   float lr;
+  const float* lr_dev;       // ABI v14: NULL, or the device fp32 that replaces lr (kEpiSgd)
   int tiles_j, tiles;
   int64_t steps_per_split;   // reduction steps of 64 per blockIdx.y
 };
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(kThreads) void linear16_bwd_kernel(const BwdArgs p)
   constexpr int FM = WTM / 16, FN = WTN / 16;
   static_assert(BM % 32 == 0 && BN % 32 == 0, "tile");
   __shared__ vec lds[2][(BM + BN) * 8];
+  const float lr = dlrm_resolve_lr(p.lr_dev, p.lr);
 
   // consecutive tiles (j fastest: they share A) go to one XCD; bijective for any count
   const int orig = blockIdx.x;
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void linear16_bwd_kernel(const BwdArgs p)
         if (p.epi == kEpiDgrad) {
           if (p.mask) v = p.mask[ci * p.ldmask + cj] > 0.f ? v : 0.f;  // selects, NaN -> 0
         } else if (p.epi == kEpiSgd) {
-          v = __fsub_rn(*o, __fmul_rn(p.lr, v));  // two roundings, as DLRM_EPI_SGD
+          v = __fsub_rn(*o, __fmul_rn(lr, v));  // two roundings, as DLRM_EPI_SGD
         }
         *o = v;
       }
@@ -212,8 +214,9 @@ __global__ __launch_bounds__(kThreads) void linear16_bwd_kernel(const BwdArgs p)
 
 // C[n][k] (op)= sum over the splits, in split order
 __global__ __launch_bounds__(kThreads) void wgrad16_reduce_kernel(
-    int64_t N, int64_t K, const float* __restrict__ partial, int splits, int sgd, float lr,
-    float* __restrict__ C, int64_t ldc) {
+    int64_t N, int64_t K, const float* __restrict__ partial, int splits, int sgd, float lr_host,
+    float* __restrict__ C, int64_t ldc, const float* __restrict__ lr_dev) {
+  const float lr = dlrm_resolve_lr(lr_dev, lr_host);
   const int64_t idx = int64_t(blockIdx.x) * kThreads + threadIdx.x;
   if (idx >= N * K) return;
   float acc = partial[idx];
@@ -368,11 +371,11 @@ extern "C" size_t dlrm_linear16_wgrad_workspace_size(int32_t type, int64_t M, in
   return size_t(w.splits) * size_t(N) * size_t(K) * sizeof(float);
 }
 
-extern "C" int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K,
-                                   const float* dY, int64_t lddy, const float* X, int64_t ldx,
-                                   int32_t mode, float lr, float* C, int64_t ldc,
-                                   void* workspace, size_t workspace_bytes,
-                                   dlrm_stream_t stream) {
+namespace {
+int linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K, const float* dY, int64_t lddy,
+                   const float* X, int64_t ldx, int32_t mode, float lr, const float* lr_dev,
+                   float* C, int64_t ldc, void* workspace, size_t workspace_bytes,
+                   dlrm_stream_t stream) {
   using namespace dlrm;
   DLRM_ARG(type == DLRM_MLP16_BF16 || type == DLRM_MLP16_F16,
            "dlrm_linear16_wgrad: unknown type %d", (int)type);
@@ -403,7 +406,7 @@ extern "C" int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K
   a.Out = split ? static_cast<float*>(workspace) : C;
   a.ldo = split ? K : ldc;
   a.epi = split ? kEpiPartial : (mode == DLRM_WGRAD16_SGD ? kEpiSgd : kEpiStore);
-  a.lr = lr;
+  a.lr = lr, a.lr_dev = lr_dev;
   a.tiles_j = int(ceil_div(K, w.tile.bn));
   a.tiles = int(ceil_div(N, w.tile.bm)) * a.tiles_j;
   a.steps_per_split = w.steps;
@@ -417,8 +420,29 @@ extern "C" int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K
   if (split) {
     hipLaunchKernelGGL(wgrad16_reduce_kernel, dim3(unsigned(ceil_div(N * K, kThreads))),
                        dim3(kThreads), 0, s, N, K, static_cast<const float*>(workspace),
-                       w.splits, int(mode == DLRM_WGRAD16_SGD), lr, C, ldc);
+                       w.splits, int(mode == DLRM_WGRAD16_SGD), lr, C, ldc, lr_dev);
     DLRM_LAUNCH_CHECK("dlrm_linear16_wgrad (reduce)");
   }
   return DLRM_OK;
+}
+}  // namespace
+
+extern "C" int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K,
+                                   const float* dY, int64_t lddy, const float* X, int64_t ldx,
+                                   int32_t mode, float lr, float* C, int64_t ldc,
+                                   void* workspace, size_t workspace_bytes,
+                                   dlrm_stream_t stream) {
+  return linear16_wgrad(type, M, N, K, dY, lddy, X, ldx, mode, lr, nullptr, C, ldc, workspace,
+                        workspace_bytes, stream);
+}
+
+extern "C" int dlrm_linear16_wgrad_dev(int32_t type, int64_t M, int64_t N, int64_t K,
+                                       const float* dY, int64_t lddy, const float* X,
+                                       int64_t ldx, int32_t mode, const float* lr_dev, float* C,
+                                       int64_t ldc, void* workspace, size_t workspace_bytes,
+                                       dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev && mode == DLRM_WGRAD16_SGD,
+           "dlrm_linear16_wgrad_dev: null lr_dev, or a mode other than DLRM_WGRAD16_SGD");
+  return linear16_wgrad(type, M, N, K, dY, lddy, X, ldx, mode, 0.f, lr_dev, C, ldc, workspace,
+                        workspace_bytes, stream);
 }

@@ -41,7 +41,9 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(int64_t N, int64_t MS
                                                            float alpha, float* __restrict__ out,
                                                            int accumulate,
                                                            float* __restrict__ sgd_param,
-                                                           float lr) {
+                                                           float lr_host,
+                                                           const float* __restrict__ lr_dev) {
+  const float lr = dlrm_resolve_lr(lr_dev, lr_host);
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   float s = 0.f;
@@ -160,12 +162,13 @@ __global__ __launch_bounds__(256) void head_fused_rows_kernel(
 __global__ __launch_bounds__(256) void head_finalize_kernel(int64_t M, int64_t K, int64_t nblk,
                                                             const float* __restrict__ part,
                                                             float* __restrict__ w, float lr,
+                                                            const float* __restrict__ lr_dev,
                                                             float* __restrict__ dw, int accumulate,
                                                             const float* __restrict__ row_loss,
                                                             float* __restrict__ loss_out) {
   __shared__ float red[4];
-  head_finalize_body(M, K, nblk, part, w, lr, dw, accumulate, row_loss, loss_out, blockIdx.x,
-                     gridDim.x, red);
+  head_finalize_body(M, K, nblk, part, w, dlrm_resolve_lr(lr_dev, lr), dw, accumulate, row_loss,
+                     loss_out, blockIdx.x, gridDim.x, red);
 }
 
 __global__ __launch_bounds__(256) void mean_kernel(int64_t M, const float* __restrict__ v,
@@ -198,7 +201,9 @@ __global__ __launch_bounds__(256) void outer_drelu_kernel(int64_t M, int64_t K,
 
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
                                                   const float* __restrict__ g, int64_t n,
-                                                  float lr) {
+                                                  float lr_host,
+                                                  const float* __restrict__ lr_dev) {
+  const float lr = dlrm_resolve_lr(lr_dev, lr_host);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = i; j < n; j += stride) p[j] = fmaf(-lr, g[j], p[j]);
@@ -207,7 +212,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
 __global__ __launch_bounds__(256) void adagrad_kernel(float* __restrict__ p,
                                                       const float* __restrict__ g,
                                                       float* __restrict__ ss, int64_t n,
-                                                      float clr, float eps, float gs) {
+                                                      float clr_host, float eps, float gs,
+                                                      const float* __restrict__ clr_dev) {
+  const float clr = dlrm_resolve_lr(clr_dev, clr_host);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = i; j < n; j += stride) {
@@ -295,11 +302,10 @@ extern "C" size_t dlrm_colsum_workspace_size(int64_t M, int64_t N) {
   return (size_t)(ms * (N > 0 ? N : 1)) * sizeof(float) + 256;
 }
 
-extern "C" int dlrm_colsum_f32(int64_t M, int64_t N, const float* Y, int64_t ldy,
-                               const float* scale, float alpha, float* out, int32_t accumulate,
-                               float* sgd_param, float lr, void* workspace,
-                               size_t workspace_bytes, dlrm_stream_t stream) {
-  const char* name = "dlrm_colsum_f32";
+namespace {
+int colsum(int64_t M, int64_t N, const float* Y, int64_t ldy, const float* scale, float alpha,
+           float* out, int32_t accumulate, float* sgd_param, float lr, const float* lr_dev,
+           void* workspace, size_t workspace_bytes, dlrm_stream_t stream, const char* name) {
   DLRM_ARG(M >= 0 && N >= 0, "%s: negative size", name);
   if (N == 0) return DLRM_OK;
   DLRM_ARG(M == 0 || (Y && ldy >= N), "%s: bad Y", name);
@@ -316,9 +322,28 @@ extern "C" int dlrm_colsum_f32(int64_t M, int64_t N, const float* Y, int64_t ldy
     DLRM_LAUNCH_CHECK(name);
   }
   hipLaunchKernelGGL(colsum_final_kernel, dim3(dlrm::ceil_div(N, 256)), dim3(256), 0, st, N, ms,
-                     part, alpha, out, accumulate, sgd_param, lr);
+                     part, alpha, out, accumulate, sgd_param, lr, lr_dev);
   DLRM_LAUNCH_CHECK(name);
   return DLRM_OK;
+}
+}  // namespace
+
+extern "C" int dlrm_colsum_f32(int64_t M, int64_t N, const float* Y, int64_t ldy,
+                               const float* scale, float alpha, float* out, int32_t accumulate,
+                               float* sgd_param, float lr, void* workspace,
+                               size_t workspace_bytes, dlrm_stream_t stream) {
+  return colsum(M, N, Y, ldy, scale, alpha, out, accumulate, sgd_param, lr, nullptr, workspace,
+                workspace_bytes, stream, "dlrm_colsum_f32");
+}
+
+extern "C" int dlrm_colsum_f32_dev(int64_t M, int64_t N, const float* Y, int64_t ldy,
+                                   const float* scale, float alpha, float* out,
+                                   int32_t accumulate, float* sgd_param, const float* lr_dev,
+                                   void* workspace, size_t workspace_bytes,
+                                   dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_colsum_f32_dev: null lr_dev");
+  return colsum(M, N, Y, ldy, scale, alpha, out, accumulate, sgd_param, 0.f, lr_dev, workspace,
+                workspace_bytes, stream, "dlrm_colsum_f32_dev");
 }
 
 extern "C" size_t dlrm_head_workspace_size(int64_t M) {
@@ -367,38 +392,69 @@ extern "C" int dlrm_outer_drelu(int64_t M, int64_t K, const float* dz, const flo
   return DLRM_OK;
 }
 
+namespace {
+int sgd_update(float* param, const float* grad, int64_t n, float lr, const float* lr_dev,
+               dlrm_stream_t stream, const char* name) {
+  DLRM_ARG(n >= 0, "%s: bad n", name);
+  if (n == 0) return DLRM_OK;
+  DLRM_ARG(param && grad, "%s: null pointer", name);
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
+                     dlrm::as_stream(stream), param, grad, n, lr, lr_dev);
+  DLRM_LAUNCH_CHECK(name);
+  return DLRM_OK;
+}
+
+int adagrad_update(float* param, const float* grad, float* state_sum, int64_t n, float gs,
+                   float clr, const float* clr_dev, float eps, dlrm_stream_t stream,
+                   const char* name) {
+  DLRM_ARG(n >= 0, "%s: bad n", name);
+  if (n == 0) return DLRM_OK;
+  DLRM_ARG(param && grad && state_sum, "%s: null pointer", name);
+  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
+                     dlrm::as_stream(stream), param, grad, state_sum, n, clr, eps, gs, clr_dev);
+  DLRM_LAUNCH_CHECK(name);
+  return DLRM_OK;
+}
+}  // namespace
+
 extern "C" int dlrm_sgd_update(float* param, const float* grad, int64_t n, float lr,
                                dlrm_stream_t stream) {
-  DLRM_ARG(n >= 0, "dlrm_sgd_update: bad n");
-  if (n == 0) return DLRM_OK;
-  DLRM_ARG(param && grad, "dlrm_sgd_update: null pointer");
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
-                     dlrm::as_stream(stream), param, grad, n, lr);
-  DLRM_LAUNCH_CHECK("dlrm_sgd_update");
-  return DLRM_OK;
+  return sgd_update(param, grad, n, lr, nullptr, stream, "dlrm_sgd_update");
+}
+
+extern "C" int dlrm_sgd_update_dev(float* param, const float* grad, int64_t n,
+                                   const float* lr_dev, dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_sgd_update_dev: null lr_dev");
+  return sgd_update(param, grad, n, 0.f, lr_dev, stream, "dlrm_sgd_update_dev");
 }
 
 extern "C" int dlrm_adagrad_update(float* param, const float* grad, float* state_sum, int64_t n,
                                    float clr, float eps, dlrm_stream_t stream) {
-  DLRM_ARG(n >= 0, "dlrm_adagrad_update: bad n");
-  if (n == 0) return DLRM_OK;
-  DLRM_ARG(param && grad && state_sum, "dlrm_adagrad_update: null pointer");
-  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
-                     dlrm::as_stream(stream), param, grad, state_sum, n, clr, eps, 1.0f);
-  DLRM_LAUNCH_CHECK("dlrm_adagrad_update");
-  return DLRM_OK;
+  return adagrad_update(param, grad, state_sum, n, 1.0f, clr, nullptr, eps, stream,
+                        "dlrm_adagrad_update");
+}
+
+extern "C" int dlrm_adagrad_update_dev(float* param, const float* grad, float* state_sum,
+                                       int64_t n, const float* clr_dev, float eps,
+                                       dlrm_stream_t stream) {
+  DLRM_ARG(clr_dev, "dlrm_adagrad_update_dev: null clr_dev");
+  return adagrad_update(param, grad, state_sum, n, 1.0f, 0.f, clr_dev, eps, stream,
+                        "dlrm_adagrad_update_dev");
 }
 
 extern "C" int dlrm_adagrad_update_scaled(float* param, const float* grad, float* state_sum,
                                           int64_t n, float grad_scale, float clr, float eps,
                                           dlrm_stream_t stream) {
-  DLRM_ARG(n >= 0, "dlrm_adagrad_update_scaled: bad n");
-  if (n == 0) return DLRM_OK;
-  DLRM_ARG(param && grad && state_sum, "dlrm_adagrad_update_scaled: null pointer");
-  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
-                     dlrm::as_stream(stream), param, grad, state_sum, n, clr, eps, grad_scale);
-  DLRM_LAUNCH_CHECK("dlrm_adagrad_update_scaled");
-  return DLRM_OK;
+  return adagrad_update(param, grad, state_sum, n, grad_scale, clr, nullptr, eps, stream,
+                        "dlrm_adagrad_update_scaled");
+}
+
+extern "C" int dlrm_adagrad_update_scaled_dev(float* param, const float* grad, float* state_sum,
+                                              int64_t n, float grad_scale, const float* clr_dev,
+                                              float eps, dlrm_stream_t stream) {
+  DLRM_ARG(clr_dev, "dlrm_adagrad_update_scaled_dev: null clr_dev");
+  return adagrad_update(param, grad, state_sum, n, grad_scale, 0.f, clr_dev, eps, stream,
+                        "dlrm_adagrad_update_scaled_dev");
 }
 
 extern "C" int dlrm_scale_f32(float* x, int64_t n, float alpha, dlrm_stream_t stream) {
@@ -484,7 +540,7 @@ namespace {
 int head_step(int64_t M, int64_t K, const float* X, int64_t ldx, float* w, const float* target,
               int32_t loss_kind, float clamp_lo, float grad_scale, float* prob_out,
               float* dz_out, float* loss_out, float* dX, int64_t lddx, int32_t relu_mask,
-              float* dw_out, int32_t accumulate, float lr, void* workspace,
+              float* dw_out, int32_t accumulate, float lr, const float* lr_dev, void* workspace,
               size_t workspace_bytes, LaunchRole* defer, dlrm_stream_t stream, const char* name) {
   DLRM_ARG(M > 0 && K > 0, "%s: bad sizes", name);
   DLRM_ARG(X && w && ldx >= K && target, "%s: null X/w/target", name);
@@ -511,12 +567,13 @@ int head_step(int64_t M, int64_t K, const float* X, int64_t ldx, float* w, const
     defer->head.M = M, defer->head.K = K, defer->head.nblk = nblk, defer->head.part = part;
     defer->head.w = w, defer->head.dw = dw_out, defer->head.row_loss = row_loss;
     defer->head.loss_out = loss_out, defer->head.lr = lr, defer->head.accumulate = accumulate;
+    defer->head.lr_dev = lr_dev;
     defer->blocks = (int32_t)(dlrm::ceil_div(dlrm::ceil_div(K, (int64_t)4), (int64_t)8) * 8);
     defer->kind = kRoleHead;
     return DLRM_OK;
   }
   hipLaunchKernelGGL(head_finalize_kernel, dim3(dlrm::ceil_div(K, 4)), dim3(256), 0, st, M, K,
-                     nblk, part, w, lr, dw_out, accumulate, row_loss, loss_out);
+                     nblk, part, w, lr, lr_dev, dw_out, accumulate, row_loss, loss_out);
   DLRM_LAUNCH_CHECK(name);
   return DLRM_OK;
 }
@@ -530,8 +587,21 @@ extern "C" int dlrm_head_step(int64_t M, int64_t K, const float* X, int64_t ldx,
                               int32_t accumulate, float lr, void* workspace,
                               size_t workspace_bytes, dlrm_stream_t stream) {
   return head_step(M, K, X, ldx, w, target, loss_kind, clamp_lo, grad_scale, prob_out, dz_out,
-                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, lr, workspace,
+                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, lr, nullptr, workspace,
                    workspace_bytes, nullptr, stream, "dlrm_head_step");
+}
+
+extern "C" int dlrm_head_step_dev(int64_t M, int64_t K, const float* X, int64_t ldx, float* w,
+                                  const float* target, int32_t loss_kind, float clamp_lo,
+                                  float grad_scale, float* prob_out, float* dz_out,
+                                  float* loss_out, float* dX, int64_t lddx, int32_t relu_mask,
+                                  float* dw_out, int32_t accumulate, const float* lr_dev,
+                                  void* workspace, size_t workspace_bytes,
+                                  dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_head_step_dev: null lr_dev");
+  return head_step(M, K, X, ldx, w, target, loss_kind, clamp_lo, grad_scale, prob_out, dz_out,
+                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, 0.f, lr_dev, workspace,
+                   workspace_bytes, nullptr, stream, "dlrm_head_step_dev");
 }
 
 extern "C" int dlrm_head_step_defer(int64_t M, int64_t K, const float* X, int64_t ldx, float* w,
@@ -547,7 +617,25 @@ extern "C" int dlrm_head_step_defer(int64_t M, int64_t K, const float* X, int64_
   *r = LaunchRole{};
   r->magic = kRoleMagic;
   return head_step(M, K, X, ldx, w, target, loss_kind, clamp_lo, grad_scale, prob_out, dz_out,
-                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, lr, workspace,
+                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, lr, nullptr, workspace,
+                   workspace_bytes, r, stream, name);
+}
+
+extern "C" int dlrm_head_step_defer_dev(int64_t M, int64_t K, const float* X, int64_t ldx,
+                                        float* w, const float* target, int32_t loss_kind,
+                                        float clamp_lo, float grad_scale, float* prob_out,
+                                        float* dz_out, float* loss_out, float* dX, int64_t lddx,
+                                        int32_t relu_mask, float* dw_out, int32_t accumulate,
+                                        const float* lr_dev, void* workspace,
+                                        size_t workspace_bytes, dlrm_launch_role* role,
+                                        dlrm_stream_t stream) {
+  const char* name = "dlrm_head_step_defer_dev";
+  DLRM_ARG(role && lr_dev, "%s: null role or lr_dev", name);
+  auto* r = reinterpret_cast<LaunchRole*>(role);
+  *r = LaunchRole{};
+  r->magic = kRoleMagic;
+  return head_step(M, K, X, ldx, w, target, loss_kind, clamp_lo, grad_scale, prob_out, dz_out,
+                   loss_out, dX, lddx, relu_mask, dw_out, accumulate, 0.f, lr_dev, workspace,
                    workspace_bytes, r, stream, name);
 }
 

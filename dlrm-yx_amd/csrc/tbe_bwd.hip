@@ -894,9 +894,9 @@ BwdWs<KeyT> carve_bwd_ws(void* base, int64_t N, int64_t D, int end_bit) {
 template <typename KeyT, typename IdxT, typename OffT>
 int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_base, int T, int B,
                const void* idx, const void* off, int64_t N, int64_t total_rows, const float* psw,
-               const float* gout, int64_t gbs, float lr, float eps, void* ws, size_t ws_bytes,
-               int64_t max_seg, int32_t* err, int presorted, LaunchRole* defer, hipStream_t st,
-               const char* name, bool sort_only = false) {
+               const float* gout, int64_t gbs, float lr, const float* lr_dev, float eps, void* ws,
+               size_t ws_bytes, int64_t max_seg, int32_t* err, int presorted, LaunchRole* defer,
+               hipStream_t st, const char* name, bool sort_only = false) {
   if (defer) {  // until proven fusable: nothing deferred
     *defer = LaunchRole{};
     defer->magic = kRoleMagic;
@@ -1013,7 +1013,7 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
     r.keys = reinterpret_cast<const uint32_t*>(w.keys_out);
     r.pos = w.pos_out;
     r.bag_of = per_table ? w.bag_of : w.pos_out;
-    r.D = D, r.gbs = gbs, r.N = N, r.lr = lr, r.eps = eps;
+    r.D = D, r.gbs = gbs, r.N = N, r.lr = lr, r.lr_dev = lr_dev, r.eps = eps;
     r.sentinel = (uint32_t)sentinel;
     r.B = B, r.ch = ch, r.mode = mode, r.lpb = lpb;
     // a multiple of 8 workgroups keeps the co-launched GEMM tiles' XCD remap aligned
@@ -1032,14 +1032,14 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
       hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, true>), dim3(blocks),  \
                          dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out,                \
                          per_table ? w.bag_of : w.pos_out, psw, gout, gbs, N, lr, eps,         \
-                         sentinel, w.partial, ch);                                             \
+                         sentinel, w.partial, ch, lr_dev);                                     \
     else                                                                                       \
       hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, false>), dim3(blocks), \
                          dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out, w.bag_of, psw, \
-                         gout, gbs, N, lr, eps, sentinel, w.partial, ch);                      \
+                         gout, gbs, N, lr, eps, sentinel, w.partial, ch, lr_dev);              \
     hipLaunchKernelGGL((tbe_bwd_combine_kernel<LPB, VW, MV, KeyT, MODE>), dim3(blocks),        \
                        dim3(256), 0, st, W, mom, D, w.keys_out, N, lr, eps, sentinel,          \
-                       w.partial, ch);                                                         \
+                       w.partial, ch, lr_dev);                                                 \
   } while (0)
 #define BY_LPB(VW, MODE)                             \
   switch (lpb) {                                     \
@@ -1082,7 +1082,7 @@ int bwd_dispatch(int mode, float* W, float* mom, int64_t D, const int64_t* row_b
                  int64_t total_rows, const float* psw, const float* gout, int64_t gbs, float lr,
                  float eps, void* ws, size_t ws_bytes, int64_t max_seg, int32_t* err,
                  int presorted, LaunchRole* defer, dlrm_stream_t stream, const char* name,
-                 bool sort_only = false) {
+                 bool sort_only = false, const float* lr_dev = nullptr) {
   DLRM_ARG(((W && gout) || sort_only) && row_base && (N == 0 || (idx && off)),
            "%s: null pointer", name);
   DLRM_ARG(presorted >= 0 && presorted <= DLRM_PRESORTED_ANY, "%s: bad presorted %d", name,
@@ -1101,8 +1101,8 @@ int bwd_dispatch(int mode, float* W, float* mom, int64_t D, const int64_t* row_b
                "%s: %lld rows in one call (at most 2^32 - 2)", name, (long long)total_rows);
 #define BWD(K, I, O)                                                                     \
   return launch_bwd<K, I, O>(mode, W, mom, D, row_base, T, B, idx, off, N, total_rows, psw, \
-                             gout, gbs, lr, eps, ws, ws_bytes, max_seg, err, presorted, defer, \
-                             st, name, sort_only)
+                             gout, gbs, lr, lr_dev, eps, ws, ws_bytes, max_seg, err, presorted, \
+                             defer, st, name, sort_only)
   if (ib == 32 && ob == 32) BWD(uint32_t, int32_t, int32_t);
   if (ib == 32 && ob == 64) BWD(uint32_t, int32_t, int64_t);
   if (ib == 64 && ob == 32) BWD(uint32_t, int64_t, int32_t);
@@ -1136,6 +1136,24 @@ extern "C" int dlrm_tbe_backward_sgd(float* weights, int64_t D, const int64_t* r
                       "dlrm_tbe_backward_sgd");
 }
 
+extern "C" int dlrm_tbe_backward_sgd_dev(float* weights, int64_t D, const int64_t* row_base,
+                                         int32_t T, int32_t B, const void* indices,
+                                         int32_t index_bits, const void* offsets,
+                                         int32_t offset_bits, int64_t num_lookups,
+                                         int64_t total_rows, const float* per_sample_weights,
+                                         const float* grad_out, int64_t grad_batch_stride,
+                                         const float* lr_dev, int64_t max_lookups_per_table,
+                                         void* workspace, size_t workspace_bytes,
+                                         int32_t* error_flag, int32_t presorted,
+                                         dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_tbe_backward_sgd_dev: null lr_dev");
+  return bwd_dispatch(MODE_SGD, weights, nullptr, D, row_base, T, B, indices, index_bits,
+                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
+                      grad_out, grad_batch_stride, 0.f, 0.f, workspace, workspace_bytes,
+                      max_lookups_per_table, error_flag, presorted, nullptr, stream,
+                      "dlrm_tbe_backward_sgd_dev", false, lr_dev);
+}
+
 extern "C" int dlrm_tbe_backward_sgd_f16(void* weights, int64_t D, const int64_t* row_base,
                                          int32_t T, int32_t B, const void* indices,
                                          int32_t index_bits, const void* offsets,
@@ -1166,6 +1184,22 @@ extern "C" int dlrm_tbe_backward_rowwise_adagrad(
                       grad_out, grad_batch_stride, lr, eps, workspace, workspace_bytes,
                       max_lookups_per_table, error_flag, presorted, nullptr, stream,
                       "dlrm_tbe_backward_rowwise_adagrad");
+}
+
+extern "C" int dlrm_tbe_backward_rowwise_adagrad_dev(
+    float* weights, float* momentum, int64_t D, const int64_t* row_base, int32_t T, int32_t B,
+    const void* indices, int32_t index_bits, const void* offsets, int32_t offset_bits,
+    int64_t num_lookups, int64_t total_rows, const float* per_sample_weights,
+    const float* grad_out, int64_t grad_batch_stride, const float* lr_dev, float eps,
+    int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes, int32_t* error_flag,
+    int32_t presorted, dlrm_stream_t stream) {
+  const char* name = "dlrm_tbe_backward_rowwise_adagrad_dev";
+  DLRM_ARG(momentum && lr_dev, "%s: null momentum or lr_dev", name);
+  return bwd_dispatch(MODE_ADAGRAD, weights, momentum, D, row_base, T, B, indices, index_bits,
+                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
+                      grad_out, grad_batch_stride, 0.f, eps, workspace, workspace_bytes,
+                      max_lookups_per_table, error_flag, presorted, nullptr, stream, name, false,
+                      lr_dev);
 }
 
 extern "C" int dlrm_tbe_backward_dense(float* grad_weights, int64_t D, const int64_t* row_base,
@@ -1201,14 +1235,15 @@ extern "C" int dlrm_tbe_backward_sort(int64_t D, const int64_t* row_base, int32_
                       "dlrm_tbe_backward_sort", true);
 }
 
-extern "C" int dlrm_tbe_backward_defer(
+namespace {
+int backward_defer(
     int32_t mode, float* weights, float* momentum, int64_t D, const int64_t* row_base,
     int32_t T, int32_t B, const void* indices, int32_t index_bits, const void* offsets,
     int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
     const float* per_sample_weights, const float* grad_out, int64_t grad_batch_stride, float lr,
-    float eps, int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes,
-    int32_t* error_flag, int32_t presorted, dlrm_launch_role* role, dlrm_stream_t stream) {
-  const char* name = "dlrm_tbe_backward_defer";
+    const float* lr_dev, float eps, int64_t max_lookups_per_table, void* workspace,
+    size_t workspace_bytes, int32_t* error_flag, int32_t presorted, dlrm_launch_role* role,
+    dlrm_stream_t stream, const char* name) {
   DLRM_ARG(role, "%s: null role", name);
   DLRM_ARG(mode == 0 || mode == 1, "%s: mode must be 0 (sgd) or 1 (rowwise adagrad)", name);
   DLRM_ARG(mode == 0 || momentum, "%s: rowwise adagrad needs momentum", name);
@@ -1219,7 +1254,38 @@ extern "C" int dlrm_tbe_backward_defer(
                       D, row_base, T, B, indices, index_bits, offsets, offset_bits, num_lookups,
                       total_rows, per_sample_weights, grad_out, grad_batch_stride, lr, eps,
                       workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted, r,
-                      stream, name);
+                      stream, name, false, lr_dev);
+}
+}  // namespace
+
+extern "C" int dlrm_tbe_backward_defer(
+    int32_t mode, float* weights, float* momentum, int64_t D, const int64_t* row_base,
+    int32_t T, int32_t B, const void* indices, int32_t index_bits, const void* offsets,
+    int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
+    const float* per_sample_weights, const float* grad_out, int64_t grad_batch_stride, float lr,
+    float eps, int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes,
+    int32_t* error_flag, int32_t presorted, dlrm_launch_role* role, dlrm_stream_t stream) {
+  return backward_defer(mode, weights, momentum, D, row_base, T, B, indices, index_bits, offsets,
+                        offset_bits, num_lookups, total_rows, per_sample_weights, grad_out,
+                        grad_batch_stride, lr, nullptr, eps, max_lookups_per_table, workspace,
+                        workspace_bytes, error_flag, presorted, role, stream,
+                        "dlrm_tbe_backward_defer");
+}
+
+extern "C" int dlrm_tbe_backward_defer_dev(
+    int32_t mode, float* weights, float* momentum, int64_t D, const int64_t* row_base,
+    int32_t T, int32_t B, const void* indices, int32_t index_bits, const void* offsets,
+    int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
+    const float* per_sample_weights, const float* grad_out, int64_t grad_batch_stride,
+    const float* lr_dev, float eps, int64_t max_lookups_per_table, void* workspace,
+    size_t workspace_bytes, int32_t* error_flag, int32_t presorted, dlrm_launch_role* role,
+    dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_tbe_backward_defer_dev: null lr_dev");
+  return backward_defer(mode, weights, momentum, D, row_base, T, B, indices, index_bits, offsets,
+                        offset_bits, num_lookups, total_rows, per_sample_weights, grad_out,
+                        grad_batch_stride, 0.f, lr_dev, eps, max_lookups_per_table, workspace,
+                        workspace_bytes, error_flag, presorted, role, stream,
+                        "dlrm_tbe_backward_defer_dev");
 }
 
 extern "C" int32_t dlrm_role_blocks(const dlrm_launch_role* role) {

@@ -467,18 +467,20 @@ __global__ __launch_bounds__(256) void tbe_bwd_block_kernel(
     const KeyT* __restrict__ keys, const int32_t* __restrict__ pos,
     const int32_t* __restrict__ bag_of, const float* __restrict__ psw,
     const float* __restrict__ gout, int64_t gbs, int64_t N, float lr, float eps,
-    KeyT sentinel, float* __restrict__ partial, int ch) {
+    KeyT sentinel, float* __restrict__ partial, int ch, const float* __restrict__ lr_dev) {
   tbe_bwd_block_body<LPB, VW, MAXV, KeyT, MODE, SB>(W, mom, D, B, keys, pos, bag_of, psw, gout,
-                                                    gbs, N, lr, eps, sentinel, partial, ch,
-                                                    blockIdx.x, gridDim.x);
+                                                    gbs, N, dlrm_resolve_lr(lr_dev, lr), eps,
+                                                    sentinel, partial, ch, blockIdx.x, gridDim.x);
 }
 
 template <int LPB, int VW, int MAXV, typename KeyT, int MODE>
 __global__ __launch_bounds__(256) void tbe_bwd_combine_kernel(
     float* __restrict__ W, float* __restrict__ mom, int64_t D, const KeyT* __restrict__ keys,
-    int64_t N, float lr, float eps, KeyT sentinel, const float* __restrict__ partial, int ch) {
-  tbe_bwd_combine_body<LPB, VW, MAXV, KeyT, MODE>(W, mom, D, keys, N, lr, eps, sentinel, partial,
-                                                  ch, blockIdx.x, gridDim.x);
+    int64_t N, float lr, float eps, KeyT sentinel, const float* __restrict__ partial, int ch,
+    const float* __restrict__ lr_dev) {
+  tbe_bwd_combine_body<LPB, VW, MAXV, KeyT, MODE>(W, mom, D, keys, N,
+                                                  dlrm_resolve_lr(lr_dev, lr), eps, sentinel,
+                                                  partial, ch, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------ deferred update --
@@ -515,7 +517,9 @@ struct LaunchRole {
     float* loss_out;
     float lr;
     int32_t accumulate;
+    const float* lr_dev;  // ABI v14: NULL, or the device fp32 that replaces lr
   } head;
+  const float* lr_dev;  // ABI v14: NULL, or the device fp32 that replaces lr (phases 1, 2)
 };
 // (phase 3, the per-table sort as a role, is gone: measured slower than the sort in the
 // lookup launch at C3, C2 and B = 256, profiles/r04_sort_role_ab.txt; ABI v7)
@@ -531,13 +535,14 @@ inline bool tbe_role_fusable(int mode, int lpb, const float* psw, int64_t grad_e
 
 template <int PHASE, int LPB, int MODE>
 __device__ __forceinline__ void tbe_role_pass(const LaunchRole& r, int blk) {
+  const float lr = dlrm_resolve_lr(r.lr_dev, r.lr);
   if constexpr (PHASE == 1)
     tbe_bwd_block_body<LPB, 4, 1, uint32_t, MODE, true, 4, true>(r.W, r.mom, r.D, r.B, r.keys, r.pos,
                                                         r.bag_of, r.psw, r.gout, r.gbs, r.N,
-                                                        r.lr, r.eps, r.sentinel, r.partial, r.ch,
+                                                        lr, r.eps, r.sentinel, r.partial, r.ch,
                                                         blk, r.blocks);
   else
-    tbe_bwd_combine_body<LPB, 4, 1, uint32_t, MODE, 8>(r.W, r.mom, r.D, r.keys, r.N, r.lr, r.eps,
+    tbe_bwd_combine_body<LPB, 4, 1, uint32_t, MODE, 8>(r.W, r.mom, r.D, r.keys, r.N, lr, r.eps,
                                                     r.sentinel, r.partial, r.ch, blk, r.blocks);
 }
 
@@ -552,8 +557,8 @@ __device__ __forceinline__ void tbe_role_lpb(const LaunchRole& r, int blk) {
 template <int PHASE>
 __device__ __forceinline__ void tbe_role_run(const LaunchRole& r, int blk, void* lds) {
   if constexpr (PHASE == 4) {
-    head_finalize_body(r.head.M, r.head.K, r.head.nblk, r.head.part, r.head.w, r.head.lr,
-                       r.head.dw, r.head.accumulate, r.head.row_loss, r.head.loss_out, blk,
+    head_finalize_body(r.head.M, r.head.K, r.head.nblk, r.head.part, r.head.w,
+                       dlrm_resolve_lr(r.head.lr_dev, r.head.lr), r.head.dw, r.head.accumulate, r.head.row_loss, r.head.loss_out, blk,
                        r.blocks, static_cast<float*>(lds));
     return;
   }

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 13
+ABI_VERSION = 14
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -36,7 +36,7 @@ class GemmProblem(ctypes.Structure):
                 ("B", c_void_p), ("ldb", c_int64), ("C", c_void_p), ("ldc", c_int64),
                 ("epilogue", c_int32), ("bias", c_void_p), ("aux", c_void_p),
                 ("ld_aux", c_int64), ("ones_col", c_int64), ("mode", c_int32),
-                ("splits", c_int32), ("partial", c_void_p)]
+                ("splits", c_int32), ("partial", c_void_p), ("alpha_dev", c_void_p)]
 
 
 MLP_MAX_LAYERS = 4
@@ -168,6 +168,34 @@ SIGNATURES = {
     "dlrm_linear16_wgrad_workspace_size": (c_size_t, [c_int32, c_int64, c_int64, c_int64]),
     "dlrm_linear16_wgrad": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
                                       c_int64, c_int32, c_float, P, c_int64, P, c_size_t, P]),
+    # ABI v14: device-resident learning rates (the host float replaced by a device pointer)
+    "dlrm_lr_state_bytes": (c_size_t, []),
+    "dlrm_lr_state_init": (c_int32, [P, c_int64, c_int64, c_int64, c_int64, c_int32, P, P]),
+    "dlrm_lr_schedule_tick": (c_int32, [P, P]),
+    "dlrm_sgd_update_dev": (c_int32, [P, P, c_int64, P, P]),
+    "dlrm_adagrad_update_dev": (c_int32, [P, P, P, c_int64, P, c_float, P]),
+    "dlrm_adagrad_update_scaled_dev": (c_int32, [P, P, P, c_int64, c_float, P, c_float, P]),
+    "dlrm_colsum_f32_dev": (c_int32, [c_int64, c_int64, P, c_int64, P, c_float, P, c_int32, P,
+                                      P, P, c_size_t, P]),
+    "dlrm_head_step_dev": (c_int32, [c_int64, c_int64, P, c_int64, P, P, c_int32, c_float,
+                                     c_float, P, P, P, P, c_int64, c_int32, P, c_int32, P, P,
+                                     c_size_t, P]),
+    "dlrm_head_step_defer_dev": (c_int32, [c_int64, c_int64, P, c_int64, P, P, c_int32, c_float,
+                                           c_float, P, P, P, P, c_int64, c_int32, P, c_int32,
+                                           P, P, c_size_t, P, P]),
+    "dlrm_tbe_backward_sgd_dev": (c_int32, [P, c_int64, P, c_int32, c_int32, P, c_int32, P,
+                                            c_int32, c_int64, c_int64, P, P, c_int64, P,
+                                            c_int64, P, c_size_t, P, c_int32, P]),
+    "dlrm_tbe_backward_rowwise_adagrad_dev": (c_int32, [P, P, c_int64, P, c_int32, c_int32, P,
+                                                        c_int32, P, c_int32, c_int64, c_int64,
+                                                        P, P, c_int64, P, c_float, c_int64, P,
+                                                        c_size_t, P, c_int32, P]),
+    "dlrm_tbe_backward_defer_dev": (c_int32, [c_int32, P, P, c_int64, P, c_int32, c_int32, P,
+                                              c_int32, P, c_int32, c_int64, c_int64, P, P,
+                                              c_int64, P, c_float, c_int64, P, c_size_t, P,
+                                              c_int32, P, P]),
+    "dlrm_linear16_wgrad_dev": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
+                                          c_int64, c_int32, P, P, c_int64, P, c_size_t, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

@@ -116,6 +116,19 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _lr_dev(lr, what: str = "lr"):
+    """A learning-rate argument is a Python float (baked into the kernel arguments, so into a
+    captured graph) or a 1-element fp32 device tensor, e.g. ``LRState.lr(k)`` (ABI v14: read
+    when the kernel runs; the caller keeps it alive and orders its writer before the
+    consumer).  Returns the tensor's device pointer, or None for a float."""
+    if not isinstance(lr, torch.Tensor):
+        return None
+    if lr.dtype != torch.float32 or lr.numel() != 1 or not lr.is_cuda:
+        raise ValueError(f"{what}: a float or a 1-element fp32 device tensor "
+                         f"(got {lr.dtype}, {lr.numel()} elements, {lr.device})")
+    return ctypes.c_void_p(lr.data_ptr())
+
+
 def _stream(device: Optional[torch.device] = None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -343,7 +356,7 @@ def tbe_backward_sort(weights: torch.Tensor, row_base: torch.Tensor, T: int, B: 
 
 def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
                  indices: torch.Tensor, offsets: torch.Tensor, grad_out: torch.Tensor,
-                 lr: float = 0.0, eps: float = 0.0, momentum: Optional[torch.Tensor] = None,
+                 lr=0.0, eps: float = 0.0, momentum: Optional[torch.Tensor] = None,
                  per_sample_weights: Optional[torch.Tensor] = None,
                  grad_batch_stride: Optional[int] = None,
                  workspace: Optional[torch.Tensor] = None,
@@ -355,8 +368,10 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     sort (bitwise the same result as the device-wide radix sort).  ``error_flag``: device
     int32 that receives TBE_ERR_INDEX / TBE_ERR_TABLE_CAP bits (see check_tbe_errors).
     ``presorted``: True - the per-table sort ran in tbe_forward_presort; PRESORTED_ANY -
-    tbe_backward_sort ran for this batch."""
+    tbe_backward_sort ran for this batch.  ``lr``: a float, or (fp32 'sgd' and
+    'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
+    lr_dev = _lr_dev(lr, "tbe_backward: lr")
     D = weights.shape[1]
     N = indices.numel()
     total_rows = weights.shape[0]
@@ -371,11 +386,20 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     st = _stream(weights.device)
     mx = int(max_lookups_per_table)
     if mode == "sgd" and weights.dtype == torch.float16:
+        if lr_dev is not None:
+            raise ValueError("tbe_backward: fp16 tables take a host float lr")
         _lib.call("dlrm_tbe_backward_sgd_f16", _p(weights), *args_common, lr, mx,
+                  _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
+    elif mode == "sgd" and lr_dev is not None:
+        _lib.call("dlrm_tbe_backward_sgd_dev", _p(weights), *args_common, lr_dev, mx,
                   _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
     elif mode == "sgd":
         _lib.call("dlrm_tbe_backward_sgd", _p(weights), *args_common, lr, mx, _p(workspace),
                   workspace.numel(), _p(error_flag), int(presorted), st)
+    elif mode == "rowwise_adagrad" and lr_dev is not None:
+        _lib.call("dlrm_tbe_backward_rowwise_adagrad_dev", _p(weights), _p(momentum),
+                  *args_common, lr_dev, eps, mx, _p(workspace), workspace.numel(),
+                  _p(error_flag), int(presorted), st)
     elif mode == "rowwise_adagrad":
         _lib.call("dlrm_tbe_backward_rowwise_adagrad", _p(weights), _p(momentum), *args_common,
                   lr, eps, mx, _p(workspace), workspace.numel(), _p(error_flag), int(presorted),
@@ -389,7 +413,7 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
 
 def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
                        indices: torch.Tensor, offsets: torch.Tensor, grad_out: torch.Tensor,
-                       lr: float = 0.0, eps: float = 0.0,
+                       lr=0.0, eps: float = 0.0,
                        momentum: Optional[torch.Tensor] = None,
                        per_sample_weights: Optional[torch.Tensor] = None,
                        grad_batch_stride: Optional[int] = None,
@@ -400,7 +424,8 @@ def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor,
     deferred (dlrm_tbe_backward_defer): returns the role to hand to gemm_group(...,
     role=, phase=1) and then phase=2 - or None when the update already ran in full (shape
     the fused passes do not cover).  The workspace, weights, momentum and grad_out must stay
-    untouched until phase 2 has run."""
+    untouched until phase 2 has run.  ``lr``: a float or a 1-element fp32 device tensor (the
+    role then carries its address: both passes read it when their launch runs)."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     if weights.dtype != torch.float32 or mode not in ("sgd", "rowwise_adagrad"):
         raise ValueError("tbe_backward_defer: fp32 'sgd' or 'rowwise_adagrad' only")
@@ -413,9 +438,12 @@ def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor,
     if workspace is None:
         workspace = _ws("tbe_bwd", need, weights.device)
     role = _lib.LaunchRole()
-    _lib.call("dlrm_tbe_backward_defer", 0 if mode == "sgd" else 1, _p(weights), _p(momentum),
+    lr_dev = _lr_dev(lr, "tbe_backward_defer: lr")
+    _lib.call("dlrm_tbe_backward_defer" if lr_dev is None else "dlrm_tbe_backward_defer_dev",
+              0 if mode == "sgd" else 1, _p(weights), _p(momentum),
               D, _p(row_base), T, B, _p(indices), _bits(indices), _p(offsets), _bits(offsets), N,
-              total_rows, _p(per_sample_weights), _p(grad_out), grad_batch_stride, lr, eps,
+              total_rows, _p(per_sample_weights), _p(grad_out), grad_batch_stride,
+              lr if lr_dev is None else lr_dev, eps,
               int(max_lookups_per_table), _p(workspace), workspace.numel(), _p(error_flag),
               int(presorted), ctypes.byref(role), _stream(weights.device))
     return role if role_blocks(role) > 0 else None
@@ -631,7 +659,7 @@ GEMM_FULL, GEMM_PARTIAL, GEMM_REDUCE = 0, 1, 2  # dlrm_gemm_mode
 
 
 def gemm_problem(A: torch.Tensor, B: torch.Tensor, trans_a: bool = False,
-                 trans_b: bool = False, C: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                 trans_b: bool = False, C: Optional[torch.Tensor] = None, alpha=1.0,
                  epilogue: int = EPI_STORE, bias: Optional[torch.Tensor] = None,
                  aux: Optional[torch.Tensor] = None, ones_col: int = -1,
                  partial: Optional[torch.Tensor] = None, splits: int = 0):
@@ -639,8 +667,10 @@ def gemm_problem(A: torch.Tensor, B: torch.Tensor, trans_a: bool = False,
     operands (unit inner stride); ones_col >= 0 also writes C[:, ones_col] =
     epilogue(alpha * op(A).sum(1)) (a Linear bias gradient).  With ``partial`` the problem
     is a PARTIAL one: K split ``splits`` ways, raw partials into ``partial``, C untouched
-    until reduce_problem(...) runs in a later launch.  Returns (struct, C)."""
+    until reduce_problem(...) runs in a later launch.  ``alpha``: a float, or a 1-element
+    fp32 device tensor (alpha_dev: read when the kernel runs).  Returns (struct, C)."""
     _check_cuda(A, B, C, bias, aux)
+    alpha_dev = _lr_dev(alpha, "gemm_problem: alpha")
     if A.stride(1) != 1 or B.stride(1) != 1:
         raise ValueError("gemm operands need unit inner stride")
     M = A.shape[1] if trans_a else A.shape[0]
@@ -656,13 +686,14 @@ def gemm_problem(A: torch.Tensor, B: torch.Tensor, trans_a: bool = False,
         raise ValueError("gemm output must be [M, >= N] with unit inner stride")
     if ones_col >= 0 and not (N <= ones_col < C.shape[1]):
         raise ValueError("ones_col must be a column of C outside [0, N)")
-    pr = _lib.GemmProblem(int(trans_a), int(trans_b), M, N, K, float(alpha), A.data_ptr(),
+    pr = _lib.GemmProblem(int(trans_a), int(trans_b), M, N, K,
+                          0.0 if alpha_dev is not None else float(alpha), A.data_ptr(),
                           A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
                           int(epilogue), bias.data_ptr() if bias is not None else None,
                           aux.data_ptr() if aux is not None else None,
                           aux.stride(0) if aux is not None else 0, int(ones_col),
                           GEMM_PARTIAL if partial is not None else GEMM_FULL, int(splits),
-                          partial.data_ptr() if partial is not None else None)
+                          partial.data_ptr() if partial is not None else None, alpha_dev)
     return pr, C
 
 
@@ -681,17 +712,19 @@ def gemm_partial_bytes(M: int, N: int, splits: int) -> int:
     return _lib.query("dlrm_gemm_f32_partial_bytes", M, N, splits)
 
 
-def sgd_job(param: torch.Tensor, grad: torch.Tensor, lr: float):
+def sgd_job(param: torch.Tensor, grad: torch.Tensor, lr):
     """param -= lr * grad (flat fp32, numel % 4 == 0, 16-B aligned) as a one-split REDUCE job:
     an elementwise GEMM-group problem, so the update rides on a launch that exists anyway
     (C = SGD(alpha * sum_s part[s]) with one split: param - lr * grad, the SGD epilogue's
-    rounding)."""
+    rounding).  ``lr``: a float or a 1-element fp32 device tensor."""
     _check_cuda(param, grad)
+    lr_dev = _lr_dev(lr, "sgd_job: lr")
     n = param.numel()
     if grad.numel() != n or n % 4 or param.data_ptr() % 16 or grad.data_ptr() % 16:
         raise ValueError("sgd_job: flat fp32 tensors of equal size, numel % 4 == 0, 16-B aligned")
-    return _lib.GemmProblem(0, 0, 1, n, 0, float(lr), None, 0, None, 0, param.data_ptr(), n,
-                            EPI_SGD, None, None, 0, -1, GEMM_REDUCE, 1, grad.data_ptr())
+    return _lib.GemmProblem(0, 0, 1, n, 0, 0.0 if lr_dev is not None else float(lr), None, 0,
+                            None, 0, param.data_ptr(), n, EPI_SGD, None, None, 0, -1,
+                            GEMM_REDUCE, 1, grad.data_ptr(), lr_dev)
 
 
 def reduce_problem(pr_partial):
@@ -739,7 +772,7 @@ def gemm_group(problems, workspace: Optional[torch.Tensor] = None, device=None, 
 
 
 def gemm(A: torch.Tensor, B: torch.Tensor, trans_a: bool = False, trans_b: bool = False,
-         C: Optional[torch.Tensor] = None, alpha: float = 1.0, epilogue: int = EPI_STORE,
+         C: Optional[torch.Tensor] = None, alpha=1.0, epilogue: int = EPI_STORE,
          bias: Optional[torch.Tensor] = None, aux: Optional[torch.Tensor] = None,
          workspace: Optional[torch.Tensor] = None, ones_col: int = -1) -> torch.Tensor:
     """C = epilogue(alpha * op(A) @ op(B)) with row-major 2-D operands (unit inner stride).
@@ -751,14 +784,17 @@ def gemm(A: torch.Tensor, B: torch.Tensor, trans_a: bool = False, trans_b: bool 
 
 def colsum(Y: torch.Tensor, scale: Optional[torch.Tensor] = None, alpha: float = 1.0,
            out: Optional[torch.Tensor] = None, accumulate: bool = False,
-           sgd_param: Optional[torch.Tensor] = None, lr: float = 0.0,
+           sgd_param: Optional[torch.Tensor] = None, lr=0.0,
            workspace: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``lr``: a float or a 1-element fp32 device tensor."""
     M, N = Y.shape
     need = _lib.query("dlrm_colsum_workspace_size", M, N)
     if workspace is None or workspace.numel() < need:
         workspace = _ws("colsum", need, Y.device)
-    _lib.call("dlrm_colsum_f32", M, N, _p(Y), Y.stride(0), _p(scale), float(alpha), _p(out),
-              int(accumulate), _p(sgd_param), float(lr), _p(workspace), workspace.numel(),
+    lr_dev = _lr_dev(lr, "colsum: lr")
+    _lib.call("dlrm_colsum_f32" if lr_dev is None else "dlrm_colsum_f32_dev", M, N, _p(Y),
+              Y.stride(0), _p(scale), float(alpha), _p(out), int(accumulate), _p(sgd_param),
+              float(lr) if lr_dev is None else lr_dev, _p(workspace), workspace.numel(),
               _stream(Y.device))
     return out
 
@@ -784,25 +820,29 @@ def head_step(X: torch.Tensor, w: torch.Tensor, target: torch.Tensor, loss: str 
               prob: Optional[torch.Tensor] = None, dz: Optional[torch.Tensor] = None,
               loss_out: Optional[torch.Tensor] = None, dX: Optional[torch.Tensor] = None,
               relu_mask: bool = True, dw: Optional[torch.Tensor] = None, accumulate: bool = False,
-              lr: float = 0.0, workspace: Optional[torch.Tensor] = None, defer: bool = False):
+              lr=0.0, workspace: Optional[torch.Tensor] = None, defer: bool = False):
     """Fused head (dlrm_head_step): X [M, K] with the folded bias column, w [K] (updated in
     place by SGD when lr != 0 and dw is None).  ``defer``: the second launch (column sums,
     update, mean loss) becomes the returned role, pass 4 of a later gemm_group
-    (dlrm_head_step_defer); w / dw / loss_out / workspace untouched until then."""
+    (dlrm_head_step_defer); w / dw / loss_out / workspace untouched until then.  ``lr``: a
+    float or a 1-element fp32 device tensor (read by the update's launch when it runs)."""
     M, K = X.shape
     need = _lib.query("dlrm_head_step_workspace_size", M, K)
     if workspace is None or workspace.numel() < need:
         workspace = _ws("head_step", need, X.device)
     _check_cuda(X, w, target)
+    lr_dev = _lr_dev(lr, "head_step: lr")
+    sfx = "" if lr_dev is None else "_dev"
     args = (M, K, _p(X), X.stride(0), _p(w), _p(target),
             LOSS_BCE if loss == "bce" else LOSS_MSE, float(clamp_lo), float(grad_scale),
             _p(prob), _p(dz), _p(loss_out), _p(dX), dX.stride(0) if dX is not None else 0,
-            int(relu_mask), _p(dw), int(accumulate), float(lr), _p(workspace), workspace.numel())
+            int(relu_mask), _p(dw), int(accumulate), float(lr) if lr_dev is None else lr_dev,
+            _p(workspace), workspace.numel())
     if defer:
         role = _lib.LaunchRole()
-        _lib.call("dlrm_head_step_defer", *args, ctypes.byref(role), _stream(X.device))
+        _lib.call("dlrm_head_step_defer" + sfx, *args, ctypes.byref(role), _stream(X.device))
         return role
-    _lib.call("dlrm_head_step", *args, _stream(X.device))
+    _lib.call("dlrm_head_step" + sfx, *args, _stream(X.device))
     return prob, dz, loss_out
 
 
@@ -913,12 +953,12 @@ def linear16_wgrad_workspace_size(M: int, N: int, K: int, dtype: str = "bf16") -
 
 
 def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
-                   lr: Optional[float] = None, dtype: str = "bf16",
+                   lr=None, dtype: str = "bf16",
                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A Linear's weight gradient on the 16-bit MFMA (dlrm_linear16_wgrad): acc [N, K] =
     r16(g)^T r16(x), g [M, N] and x [M, K] fp32 with contiguous rows, rounded to nearest-even
-    ``dtype`` in flight, fp32 accumulate.  ``lr`` None: out = acc; else the fused SGD step
-    out = out - fl(lr * acc).  Only out[:N, :K] is touched.  ``workspace`` (any contiguous
+    ``dtype`` in flight, fp32 accumulate.  ``lr`` None: out = acc; else (a float or a
+    1-element fp32 device tensor) the fused SGD step out = out - fl(lr * acc).  Only out[:N, :K] is touched.  ``workspace`` (any contiguous
     tensor of at least linear16_wgrad_workspace_size bytes) holds the partial sums when the
     planner splits the batch; it is allocated here when needed and not given.  Enqueues only."""
     if dtype not in MLP16_TYPES:
@@ -940,6 +980,12 @@ def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
     if ws_bytes < need:
         raise ValueError(f"linear16_wgrad: workspace of {ws_bytes} bytes, {need} needed")
+    lr_dev = _lr_dev(lr, "linear16_wgrad: lr")
+    if lr_dev is not None:
+        _lib.call("dlrm_linear16_wgrad_dev", MLP16_TYPES[dtype], M, N, K, _p(g), ldg, _p(x),
+                  ldx, WGRAD16_SGD, lr_dev, _p(out), ldc, _p(workspace), ws_bytes,
+                  _stream(g.device))
+        return out
     _lib.call("dlrm_linear16_wgrad", MLP16_TYPES[dtype], M, N, K, _p(g), ldg, _p(x), ldx,
               WGRAD16_STORE if lr is None else WGRAD16_SGD, 0.0 if lr is None else float(lr),
               _p(out), ldc, _p(workspace), ws_bytes, _stream(g.device))
@@ -1026,22 +1072,88 @@ def relu_backward(dy: torch.Tensor, y: torch.Tensor,
 
 
 # ----------------------------------------------------------- optimizers ----
-def sgd_update(param: torch.Tensor, grad: torch.Tensor, lr: float) -> None:
+def sgd_update(param: torch.Tensor, grad: torch.Tensor, lr) -> None:
+    """param -= lr * grad; ``lr``: a float or a 1-element fp32 device tensor."""
+    lr_dev = _lr_dev(lr, "sgd_update: lr")
+    if lr_dev is not None:
+        _lib.call("dlrm_sgd_update_dev", _p(param), _p(grad), param.numel(), lr_dev,
+                  _stream(param.device))
+        return
     _lib.call("dlrm_sgd_update", _p(param), _p(grad), param.numel(), float(lr),
               _stream(param.device))
 
 
-def adagrad_update(param: torch.Tensor, grad: torch.Tensor, state_sum: torch.Tensor, clr: float,
+def adagrad_update(param: torch.Tensor, grad: torch.Tensor, state_sum: torch.Tensor, clr,
                    eps: float, grad_scale: float = 1.0) -> None:
     """state_sum += g'^2; param -= clr * g' / (sqrt(state_sum) + eps) with g' = grad_scale * g
-    (grad itself is not modified)."""
+    (grad itself is not modified).  ``clr``: a float or a 1-element fp32 device tensor."""
+    clr_dev = _lr_dev(clr, "adagrad_update: clr")
+    sfx = "" if clr_dev is None else "_dev"
+    c = float(clr) if clr_dev is None else clr_dev
     if grad_scale != 1.0:
-        _lib.call("dlrm_adagrad_update_scaled", _p(param), _p(grad), _p(state_sum),
-                  param.numel(), float(grad_scale), float(clr), float(eps),
-                  _stream(param.device))
+        _lib.call("dlrm_adagrad_update_scaled" + sfx, _p(param), _p(grad), _p(state_sum),
+                  param.numel(), float(grad_scale), c, float(eps), _stream(param.device))
         return
-    _lib.call("dlrm_adagrad_update", _p(param), _p(grad), _p(state_sum), param.numel(),
-              float(clr), float(eps), _stream(param.device))
+    _lib.call("dlrm_adagrad_update" + sfx, _p(param), _p(grad), _p(state_sum), param.numel(),
+              c, float(eps), _stream(param.device))
+
+
+# -------------------------------------------- device-resident learning rates ----
+LR_MAX_SLOTS = 8  # DLRM_LR_MAX_SLOTS
+# byte offsets of the dlrm_lr_state block (DLRM_LR_OFF_*, include/dlrm_hip.h)
+_LR_OFF_STEP, _LR_OFF_POLICY, _LR_OFF_BASE, _LR_OFF_MULT, _LR_OFF_LR = 0, 8, 40, 104, 168
+
+
+class LRState:
+    """The dlrm_lr_state block of include/dlrm_hip.h in device memory: the scheduler's step
+    count, the policy (W, S, D), and per slot a base rate, a multiplier and the fp32 rate in
+    effect.  ``lr(k)`` is the 1-element view every ``lr`` / ``alpha`` / ``clr`` argument of
+    this module accepts; ``lr_schedule_tick`` recomputes all of them and advances the count.
+    The views alias ``buf``: writes to ``step`` / ``base`` / ``mult`` (copy_, on the stream
+    whose kernels read them) take effect at the next tick."""
+
+    def __init__(self, buf: torch.Tensor, n: int, policy):
+        self.buf, self.n, self.policy = buf, int(n), tuple(int(v) for v in policy)
+        self.step = buf[_LR_OFF_STEP:_LR_OFF_STEP + 8].view(torch.int64)
+        self.base = buf[_LR_OFF_BASE:_LR_OFF_BASE + 8 * self.n].view(torch.float64)
+        self.mult = buf[_LR_OFF_MULT:_LR_OFF_MULT + 8 * self.n].view(torch.float64)
+        self.rates = buf[_LR_OFF_LR:_LR_OFF_LR + 4 * self.n].view(torch.float32)
+
+    def lr(self, k: int) -> torch.Tensor:
+        if not 0 <= k < self.n:
+            raise IndexError(f"lr slot {k} of {self.n}")
+        return self.rates[k:k + 1]
+
+
+def lr_state(base: Sequence[float], mult: Optional[Sequence[float]] = None,
+             num_warmup_steps: int = 0, decay_start_step: int = 0, num_decay_steps: int = 0,
+             step_count: int = 1, device=None) -> LRState:
+    """A device learning-rate block (dlrm_lr_state_init + one host-to-device copy) with one
+    slot per entry of ``base``; slot k's rate is (float)(policy(step_count, base[k]) *
+    mult[k]) after each tick and (float)(base[k] * mult[k]) before the first.  All-zero
+    policy: no schedule (a tick only recomputes base * mult).  Raises ValueError for a policy
+    the reference does not run (optim.check_lr_policy)."""
+    n = len(base)
+    mult = [1.0] * n if mult is None else list(mult)
+    if not 1 <= n <= LR_MAX_SLOTS or len(mult) != n:
+        raise ValueError(f"lr_state: 1..{LR_MAX_SLOTS} slots, one multiplier each")
+    nbytes = _lib.query("dlrm_lr_state_bytes")
+    host = torch.zeros(nbytes, dtype=torch.uint8)
+    b = (ctypes.c_double * n)(*[float(v) for v in base])
+    m = (ctypes.c_double * n)(*[float(v) for v in mult])
+    try:
+        _lib.call("dlrm_lr_state_init", ctypes.c_void_p(host.data_ptr()), int(step_count),
+                  int(num_warmup_steps), int(decay_start_step), int(num_decay_steps), n, b, m)
+    except _lib.DLRMHipError as e:
+        raise ValueError(str(e)) from None
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return LRState(host.to(dev), n, (num_warmup_steps, decay_start_step, num_decay_steps))
+
+
+def lr_schedule_tick(state: LRState) -> None:
+    """One launch of one thread (dlrm_lr_schedule_tick): every slot's rate for the current
+    step count, then step count + 1.  Enqueues only; capturable."""
+    _lib.call("dlrm_lr_schedule_tick", _p(state.buf), _stream(state.buf.device))
 
 
 def scale_(x: torch.Tensor, alpha: float) -> None:

@@ -15,6 +15,43 @@ from torch.optim import Optimizer
 from . import ops
 
 
+def check_lr_policy(num_warmup_steps: int, decay_start_step: int, num_decay_steps: int) -> None:
+    """Raise ValueError for a schedule the reference does not run: a decay that starts
+    inside the warm-up (the reference sys.exit()s), or a plateau with nothing to freeze at
+    (fewer than two warm-up steps before a later decay start: the reference's ``last_lr`` is
+    never set and its get_lr raises AttributeError)."""
+    W, S, D = int(num_warmup_steps), int(decay_start_step), int(num_decay_steps)
+    if min(W, S, D) < 0:
+        raise ValueError("lr policy: negative step counts")
+    if S < W:
+        raise ValueError("Learning rate warmup must finish before the decay starts "
+                         f"(lr_decay_start_step {S} < lr_num_warmup_steps {W})")
+    if D > 0 and W < 2 and S > max(W, 1):
+        raise ValueError(f"lr policy (W={W}, S={S}, D={D}): a plateau before the decay needs at "
+                         "least two warm-up steps (the reference has no rate to freeze at)")
+
+
+def lr_policy(step_count: int, base_lr: float, num_warmup_steps: int, decay_start_step: int,
+              num_decay_steps: int) -> float:
+    """The reference's LRPolicyScheduler (dlrm_s_pytorch.py:188-222) as a closed form of its
+    ``_step_count`` (1 for the first training iteration), in Python doubles and the
+    reference's operation order: linear warm-up, a plateau frozen at the last warm-up value
+    (base * (W - 1) / W, the reference's quirk - not base), polynomial-2 decay floored at
+    1e-7, then frozen at the last decay value.  Bit-equal to the reference class
+    (tests/golden/lr_schedule.json)."""
+    sc, base = int(step_count), float(base_lr)
+    W, S, D = int(num_warmup_steps), int(decay_start_step), int(num_decay_steps)
+    check_lr_policy(W, S, D)
+    if sc < W:
+        return base * (1.0 - (W - sc) / W)
+    if D > 0:
+        if sc < S:  # between warm-up and decay: the last warm-up value
+            return base * (1.0 - (W - (W - 1)) / W)
+        ds = min(sc, S + D - 1) - S  # past the decay: its last value
+        return max(0.0000001, base * ((D - ds) / D) ** 2)
+    return base
+
+
 class RWSAdagrad(Optimizer):
     def __init__(self, params, lr=1e-2, lr_decay=0.0, weight_decay=0.0,
                  initial_accumulator_value=0.0, eps=1e-10):

@@ -23,6 +23,11 @@ optimizer update.  Layout decisions (MI355X-first):
 * Mixed precision on request (TrainerConfig.mlp_precision = "bf16"): the MLP layers below the
   head run forward, data gradient and weight gradient on the bf16 MFMA from the same fp32
   buffers (DLRMTrainer._segments16); everything above stays as described.
+* Learning-rate schedule on request (TrainerConfig.lr_num_warmup_steps / lr_decay_start_step /
+  lr_num_decay_steps, or device_lr): the step's rates live in device memory, a one-thread
+  kernel at the head of the step advances the reference's LRPolicyScheduler and every update
+  kernel reads its rate when it runs, so a captured step walks the schedule on replay.  With
+  the defaults the rates are host floats and the step is unchanged.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ import torch
 from torch.autograd.profiler import record_function
 
 from . import ops
+from .optim import check_lr_policy
 from .sharders import shard
 
 
@@ -74,8 +80,33 @@ class TrainerConfig:
     # weights and fp32 everything else (DLRMTrainer._segments16).  "fp16" would need loss
     # scaling for the gradients: not implemented
     mlp_precision: str = "fp32"
+    # the reference's LRPolicyScheduler (--lr-num-warmup-steps, --lr-decay-start-step,
+    # --lr-num-decay-steps; optim.lr_policy): linear warm-up, plateau, polynomial-2 decay,
+    # applied to learning_rate and emb_learning_rate alike.  Any of them non-zero, or
+    # device_lr, keeps the step's learning rates in device memory (lr_mode "device"): a
+    # one-thread kernel at the head of the step advances the schedule and every update
+    # kernel reads its rate from that memory, so a captured step walks the schedule on
+    # replay and DLRMTrainer.set_learning_rate reaches graphs that are already captured.
+    # All at their defaults (lr_mode "host"): the rates are host floats baked into the
+    # launches, exactly the step of before
+    lr_num_warmup_steps: int = 0
+    lr_decay_start_step: int = 0
+    lr_num_decay_steps: int = 0
+    device_lr: bool = False
+
+    @property
+    def lr_policy_steps(self):
+        return (int(self.lr_num_warmup_steps), int(self.lr_decay_start_step),
+                int(self.lr_num_decay_steps))
+
+    @property
+    def lr_mode(self) -> str:
+        """"device": learning rates in device memory (a policy, or device_lr); else "host"."""
+        return "device" if self.device_lr or any(self.lr_policy_steps) else "host"
 
     def __post_init__(self):
+        if any(self.lr_policy_steps):
+            check_lr_policy(*self.lr_policy_steps)
         if self.mlp_precision == "fp16":
             raise NotImplementedError("mlp_precision='fp16': fp16 gradients need loss scaling "
                                       "(predict(..., precision='fp16') is available)")
@@ -307,6 +338,13 @@ class DLRMTrainer:
         self._colsum_ws: Optional[torch.Tensor] = None
         self._head_ws: Optional[torch.Tensor] = None
         self.step_count = 0
+        # lr_mode "device": slot 0 the dense rate, 1 the embedding rate, 2 the dense rate / W
+        # (the dense update of the W-rank schedule); None: host floats
+        self._lr_state = None
+        if cfg.lr_mode == "device":
+            self._lr_state = ops.lr_state(
+                [self.lr, self.emb_lr, self.lr], [1.0, 1.0, 1.0 / self.world],
+                *cfg.lr_policy_steps, device=self.dev)
         self.capture_mode = None  # "whole" | "segments": how the last capture() was built
         self.graphs_per_step = 0  # hipGraphs one replay of the last capture() launches
         if init:
@@ -404,6 +442,63 @@ class DLRMTrainer:
     def emb_lr(self) -> float:
         return float(self.cfg.emb_learning_rate if self.cfg.emb_learning_rate is not None
                      else self.cfg.learning_rate)
+
+    def _rates(self):
+        """(dense rate, embedding rate, dense rate / W) as the step's launches take them:
+        host floats, or (lr_mode "device") the 1-element views of the device slots."""
+        if self._lr_state is None:
+            lr = self.lr
+            return lr, self.emb_lr, lr * (1.0 / self.world)
+        s = self._lr_state
+        return s.lr(0), s.lr(1), s.lr(2)
+
+    def _with_tick(self, fn):
+        """The step's first "gpu" segment: in lr_mode "device" it starts with the schedule's
+        tick, on the main stream before anything forks off it (the early sort's side stream
+        and the collectives wait for the main stream later, so they are ordered after it)."""
+        if self._lr_state is None:
+            return fn
+
+        def ticked():
+            ops.lr_schedule_tick(self._lr_state)
+            return fn()
+        return ticked
+
+    def set_learning_rate(self, lr: float, emb_lr: Optional[float] = None) -> None:
+        """New base learning rates (``emb_lr`` None: the embedding rate keeps following
+        ``lr`` if cfg.emb_learning_rate was never set, else stays).  lr_mode "device": the
+        bases are copied into the device block on the current stream and the next step -
+        eager, or a replay of an ALREADY CAPTURED graph - trains at them (through the policy,
+        if one is set).  lr_mode "host": cfg is updated; the next eager step and the next
+        capture() use it, graphs captured before keep the rate they were captured with."""
+        self.cfg.learning_rate = float(lr)
+        if emb_lr is not None:
+            self.cfg.emb_learning_rate = float(emb_lr)
+        if self._lr_state is not None:
+            base = torch.tensor([self.lr, self.emb_lr, self.lr], dtype=torch.float64)
+            self._lr_state.base.copy_(base)
+
+    @property
+    def lr_step(self) -> int:
+        """The device schedule's step count (the reference scheduler's _step_count: 1 before
+        the first step); synchronises.  Set it to resume a schedule."""
+        if self._lr_state is None:
+            raise RuntimeError("lr_step: no device learning-rate state (cfg.lr_mode is 'host')")
+        return int(self._lr_state.step.item())
+
+    @lr_step.setter
+    def lr_step(self, value: int) -> None:
+        if self._lr_state is None:
+            raise RuntimeError("lr_step: no device learning-rate state (cfg.lr_mode is 'host')")
+        self._lr_state.step.fill_(int(value))
+
+    def current_lr(self) -> List[float]:
+        """[dense rate, embedding rate, dense rate / W] as fp32 values: the rates the last
+        step trained at (lr_mode "device": read from the device, synchronises; before the
+        first step, base * multiplier) or the next one will (lr_mode "host")."""
+        if self._lr_state is None:
+            return [float(np.float32(v)) for v in self._rates()]
+        return [float(v) for v in self._lr_state.rates.cpu()]
 
     def local_batch_size(self, B: int) -> int:
         if B % self.world:
@@ -659,7 +754,7 @@ class DLRMTrainer:
         prof = profile or (lambda name: _NullCtx())
         self._prof = prof
         fused_opt = self.grads is None  # single GPU SGD: updates fused into backward
-        lr, elr = self.lr, self.emb_lr
+        lr, elr, lr_w = self._rates()  # host floats, or the device slots (lr_mode "device")
         conc = self.concurrent and profile is None
         dist = self.distributed
         c_fwd = conc and "fwd" in self.overlaps and not dist
@@ -991,9 +1086,9 @@ class DLRMTrainer:
                 if cfg.optimizer == "sgd" and st.pop("top_updated", False):
                     # the top bucket's update rode on the embedding update's second pass
                     nb = self.n_bot_params
-                    ops.sgd_update(self.params[:nb], self.grads[:nb], lr * scale)
+                    ops.sgd_update(self.params[:nb], self.grads[:nb], lr_w)
                 elif cfg.optimizer == "sgd":
-                    ops.sgd_update(self.params, self.grads, lr * scale)
+                    ops.sgd_update(self.params, self.grads, lr_w)
                 else:  # the 1/W folded into the update (one pass over the bucket)
                     ops.adagrad_update(self.params, self.grads, self.adagrad_sum, lr,
                                        cfg.adagrad_eps, grad_scale=scale)
@@ -1002,10 +1097,12 @@ class DLRMTrainer:
             self.step_count += 1
 
         if not dist:
-            segs = [("gpu", fwd_single), ("gpu", middle), ("gpu", backward_single)]
+            segs = [("gpu", self._with_tick(fwd_single)), ("gpu", middle),
+                    ("gpu", backward_single)]
             if not fused_opt:
                 segs.append(("gpu", dense_update))
             return segs + [("host", done)]
+        lookup = self._with_tick(lookup)
         # multi GPU (distributed_forward, dlrm_s_pytorch.py:686-730; DDP :1626-1633):
         #  * the pooled-embedding all-to-all overlaps the bottom MLP (one chain launch);
         #  * the top MLP's gradient bucket is all-reduced as soon as the top backward is
@@ -1051,7 +1148,7 @@ class DLRMTrainer:
             jobs = []
             if cfg.optimizer == "sgd":  # the top bucket was all-reduced (waited) already
                 nb = self.n_bot_params
-                jobs = [ops.sgd_job(self.params[nb:], self.grads[nb:], lr * (1.0 / self.world))]
+                jobs = [ops.sgd_job(self.params[nb:], self.grads[nb:], lr_w)]
                 st["top_updated"] = True
             self._roles = [(role, 2)]
             self._gemm(jobs)
@@ -1157,7 +1254,7 @@ class DLRMTrainer:
         prof = profile or (lambda name: _NullCtx())
         self._prof = prof
         fused_opt = self.grads is None
-        lr, elr = self.lr, self.emb_lr
+        lr, elr, lr_w = self._rates()  # host floats, or the device slots (lr_mode "device")
         conc = self.concurrent and profile is None
         dist = self.distributed
         st = {}
@@ -1333,7 +1430,7 @@ class DLRMTrainer:
             with record_function("## Backward ##"), prof("dense_update"):
                 scale = 1.0 / self.world
                 if cfg.optimizer == "sgd":
-                    ops.sgd_update(self.params, self.grads, lr * scale)
+                    ops.sgd_update(self.params, self.grads, lr_w)
                 else:
                     ops.adagrad_update(self.params, self.grads, self.adagrad_sum, lr,
                                        cfg.adagrad_eps, grad_scale=scale)
@@ -1342,10 +1439,12 @@ class DLRMTrainer:
             self.step_count += 1
 
         if not dist:
-            segs = [("gpu", fwd_single), ("gpu", middle), ("gpu", backward_single)]
+            segs = [("gpu", self._with_tick(fwd_single)), ("gpu", middle),
+                    ("gpu", backward_single)]
             if not fused_opt:
                 segs.append(("gpu", dense_update))
             return segs + [("host", done)]
+        lookup = self._with_tick(lookup)
 
         def ar(bucket):
             def start():

@@ -120,8 +120,12 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    rounded from the fp32 tensors in flight, fp32 accumulate) + DLRM_TUNE_LINEAR16_TILE.
  * 13: dlrm_linear16_dgrad, dlrm_linear16_wgrad (+ _workspace_size): the same Linear's data
  *    and weight gradients on the 16-bit MFMA, for the mixed-precision training step
- *    + DLRM_TUNE_LINEAR16_DGRAD_TILE / _WGRAD_TILE / _WGRAD_SPLIT. */
-#define DLRM_ABI_VERSION 13 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    + DLRM_TUNE_LINEAR16_DGRAD_TILE / _WGRAD_TILE / _WGRAD_SPLIT.
+ * 14: device-resident learning rates: dlrm_lr_state_* + dlrm_lr_schedule_tick (the reference's
+ *    LRPolicyScheduler advanced by a one-thread kernel), a `_dev` sibling of every entry
+ *    point that takes a learning rate (the rate read from device memory when the kernel
+ *    runs), dlrm_gemm_problem.alpha_dev. */
+#define DLRM_ABI_VERSION 14 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -606,6 +610,10 @@ typedef struct dlrm_gemm_problem {
   int32_t mode;     /* dlrm_gemm_mode */
   int32_t splits;   /* PARTIAL / REDUCE */
   float* partial;   /* PARTIAL / REDUCE */
+  const float* alpha_dev; /* ABI v14: NULL = use alpha; else a device pointer to one fp32 that
+                             replaces alpha, read when the kernel runs (see "device-resident
+                             learning rates" below); ignored by PARTIAL problems, which do
+                             not scale */
 } dlrm_gemm_problem;
 
 size_t dlrm_gemm_f32_group_workspace_size(int32_t n, const dlrm_gemm_problem* problems);
@@ -867,6 +875,115 @@ int dlrm_linear16_wgrad(int32_t type, int64_t M, int64_t N, int64_t K,
                         const float* dY, int64_t lddy, const float* X, int64_t ldx,
                         int32_t mode, float lr, float* C, int64_t ldc,
                         void* workspace, size_t workspace_bytes, dlrm_stream_t stream);
+
+/* ------------------------------------------- device-resident learning rates -- */
+/*
+ * ABI v14.  A captured hipGraph bakes every host `float lr` into its kernel arguments, so a
+ * replayed step can train at one rate only.  Each entry point that takes a learning rate has
+ * a `_dev` sibling taking `const float* lr_dev` instead: a DEVICE pointer to one fp32 (4-byte
+ * aligned, NULL not allowed), loaded once at kernel entry (a wave-uniform load) when the
+ * kernel RUNS.  Same kernels, same arithmetic: with *lr_dev == lr the result is bitwise the
+ * host-float call's.  Whoever writes *lr_dev must be ordered before the consumer (stream
+ * order, or a graph dependency).
+ *
+ * dlrm_lr_state: the rates of one trainer and the reference's LRPolicyScheduler
+ * (dlrm_s_pytorch.py:188-222; --lr-num-warmup-steps W, --lr-decay-start-step S,
+ * --lr-num-decay-steps D) in DLRM_LR_STATE_BYTES of device memory, 8-byte aligned:
+ *   offset   0  int64  step_count     the scheduler's _step_count: 1 before the first step
+ *            8  int64  W, S, D        (offsets 8, 16, 24); all 0 = no policy
+ *           32  int32  n              slots in use, <= DLRM_LR_MAX_SLOTS; int32 pad at 36
+ *           40  double base[8]        base rate of slot k
+ *          104  double mult[8]        what the host folds into the rate (e.g. 1 / world)
+ *          168  float  lr[8]          the rate in effect: &lr[k] is slot k's lr_dev
+ * dlrm_lr_schedule_tick (one thread, fp64, IEEE division, the reference's operation order)
+ * sets, with sc = step_count,
+ *   f(sc, b) = b * (1.0 - (W - sc) / W)                          sc < W          (warm-up)
+ *              f(W - 1, b)                                       D > 0, sc < S   (plateau)
+ *              max(1e-7, b * x * x), x = (D - (min(sc, S + D - 1) - S)) / D   D > 0 (decay,
+ *                                                                then frozen at its end)
+ *              b                                                 otherwise
+ *   lr[k] = (float)(f(sc, base[k]) * mult[k]),  k < n;   step_count = sc + 1
+ * - the double product rounded once to fp32, which is what passing the host double as a
+ * `float` argument does.  Replaying a graph that starts with the tick therefore walks the
+ * schedule with no host work.  S < W, and D > 0 with W < 2 and S > max(W, 1), are refused by
+ * dlrm_lr_state_init (the reference exits / raises there).
+ */
+#define DLRM_LR_MAX_SLOTS 8
+#define DLRM_LR_STATE_BYTES 200
+#define DLRM_LR_OFF_STEP 0
+#define DLRM_LR_OFF_POLICY 8
+#define DLRM_LR_OFF_N 32
+#define DLRM_LR_OFF_BASE 40
+#define DLRM_LR_OFF_MULT 104
+#define DLRM_LR_OFF_LR 168
+size_t dlrm_lr_state_bytes(void);
+/* Fills a HOST image of the block (state_host: DLRM_LR_STATE_BYTES; the caller copies it to
+ * the device): step_count, the policy, n slots of base / mult, and lr[k] =
+ * (float)(base[k] * mult[k]) (the rate of an unticked state). */
+int dlrm_lr_state_init(void* state_host, int64_t step_count, int64_t num_warmup_steps,
+                       int64_t decay_start_step, int64_t num_decay_steps, int32_t n,
+                       const double* base, const double* mult);
+int dlrm_lr_schedule_tick(void* state, dlrm_stream_t stream);
+
+int dlrm_sgd_update_dev(float* param, const float* grad, int64_t n, const float* lr_dev,
+                        dlrm_stream_t stream);
+int dlrm_adagrad_update_dev(float* param, const float* grad, float* state_sum, int64_t n,
+                            const float* clr_dev, float eps, dlrm_stream_t stream);
+int dlrm_adagrad_update_scaled_dev(float* param, const float* grad, float* state_sum,
+                                   int64_t n, float grad_scale, const float* clr_dev, float eps,
+                                   dlrm_stream_t stream);
+int dlrm_colsum_f32_dev(int64_t M, int64_t N, const float* Y, int64_t ldy, const float* scale,
+                        float alpha, float* out, int32_t accumulate, float* sgd_param,
+                        const float* lr_dev, void* workspace, size_t workspace_bytes,
+                        dlrm_stream_t stream);
+/* (dw_out == NULL: w -= *lr_dev * s unless *lr_dev == 0, as dlrm_head_step) */
+int dlrm_head_step_dev(int64_t M, int64_t K, const float* X, int64_t ldx, float* w,
+                       const float* target, int32_t loss_kind, float clamp_lo, float grad_scale,
+                       float* prob_out, float* dz_out, float* loss_out, float* dX, int64_t lddx,
+                       int32_t relu_mask, float* dw_out, int32_t accumulate,
+                       const float* lr_dev, void* workspace, size_t workspace_bytes,
+                       dlrm_stream_t stream);
+int dlrm_head_step_defer_dev(int64_t M, int64_t K, const float* X, int64_t ldx, float* w,
+                             const float* target, int32_t loss_kind, float clamp_lo,
+                             float grad_scale, float* prob_out, float* dz_out, float* loss_out,
+                             float* dX, int64_t lddx, int32_t relu_mask, float* dw_out,
+                             int32_t accumulate, const float* lr_dev, void* workspace,
+                             size_t workspace_bytes, dlrm_launch_role* role,
+                             dlrm_stream_t stream);
+int dlrm_tbe_backward_sgd_dev(float* weights, int64_t D, const int64_t* row_base, int32_t T,
+                              int32_t B, const void* indices, int32_t index_bits,
+                              const void* offsets, int32_t offset_bits, int64_t num_lookups,
+                              int64_t total_rows, const float* per_sample_weights,
+                              const float* grad_out, int64_t grad_batch_stride,
+                              const float* lr_dev, int64_t max_lookups_per_table,
+                              void* workspace, size_t workspace_bytes, int32_t* error_flag,
+                              int32_t presorted, dlrm_stream_t stream);
+int dlrm_tbe_backward_rowwise_adagrad_dev(float* weights, float* momentum, int64_t D,
+                                          const int64_t* row_base, int32_t T, int32_t B,
+                                          const void* indices, int32_t index_bits,
+                                          const void* offsets, int32_t offset_bits,
+                                          int64_t num_lookups, int64_t total_rows,
+                                          const float* per_sample_weights,
+                                          const float* grad_out, int64_t grad_batch_stride,
+                                          const float* lr_dev, float eps,
+                                          int64_t max_lookups_per_table, void* workspace,
+                                          size_t workspace_bytes, int32_t* error_flag,
+                                          int32_t presorted, dlrm_stream_t stream);
+/* (the role carries the pointer: both phases read *lr_dev when their launch runs) */
+int dlrm_tbe_backward_defer_dev(int32_t mode, float* weights, float* momentum, int64_t D,
+                                const int64_t* row_base, int32_t T, int32_t B,
+                                const void* indices, int32_t index_bits, const void* offsets,
+                                int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
+                                const float* per_sample_weights, const float* grad_out,
+                                int64_t grad_batch_stride, const float* lr_dev, float eps,
+                                int64_t max_lookups_per_table, void* workspace,
+                                size_t workspace_bytes, int32_t* error_flag, int32_t presorted,
+                                dlrm_launch_role* role, dlrm_stream_t stream);
+/* mode must be DLRM_WGRAD16_SGD */
+int dlrm_linear16_wgrad_dev(int32_t type, int64_t M, int64_t N, int64_t K, const float* dY,
+                            int64_t lddy, const float* X, int64_t ldx, int32_t mode,
+                            const float* lr_dev, float* C, int64_t ldc, void* workspace,
+                            size_t workspace_bytes, dlrm_stream_t stream);
 
 #ifdef __cplusplus
 }
