@@ -22,7 +22,7 @@ optimizer update.  Layout decisions (MI355X-first):
   MLP backward, and the dense all-reduce overlaps the embedding update.
 * Mixed precision on request (TrainerConfig.mlp_precision = "bf16"): the MLP layers below the
   head run forward, data gradient and weight gradient on the bf16 MFMA from the same fp32
-  buffers (DLRMTrainer._segments16); everything above stays as described.
+  buffers (the 16-bit closures of DLRMTrainer._build); everything above stays as described.
 * Learning-rate schedule on request (TrainerConfig.lr_num_warmup_steps / lr_decay_start_step /
   lr_num_decay_steps, or device_lr): the step's rates live in device memory, a one-thread
   kernel at the head of the step advances the reference's LRPolicyScheduler and every update
@@ -51,6 +51,12 @@ def _pad4(n: int) -> int:
     return (int(n) + 3) // 4 * 4
 
 
+def _precision(precision: str) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+    return precision
+
+
 @dataclass
 class TrainerConfig:
     m_spa: int
@@ -77,7 +83,7 @@ class TrainerConfig:
     # operands of the MLP GEMMs below the head: "fp32", or "bf16" = mixed precision - every
     # such Linear's forward, data gradient and weight gradient on the 16-bit MFMA with
     # operands rounded in flight from the fp32 tensors, fp32 accumulation, fp32 master
-    # weights and fp32 everything else (DLRMTrainer._segments16).  "fp16" would need loss
+    # weights and fp32 everything else (DLRMTrainer._build).  "fp16" would need loss
     # scaling for the gradients: not implemented
     mlp_precision: str = "fp32"
     # the reference's LRPolicyScheduler (--lr-num-warmup-steps, --lr-decay-start-step,
@@ -214,8 +220,9 @@ class DLRMTrainer:
         self._qr_pr = torch.tensor(pr, **i32)
         self._qr_csr = {}
         rows = prow
-        self.row_base = torch.tensor([0] + np.cumsum(rows).tolist(), dtype=torch.int64,
-                                     device=self.dev)
+        # row bases of the physical tables: the host copy serves _rows without a device sync
+        self._row_bases = [0] + np.cumsum(rows).tolist()
+        self.row_base = torch.tensor(self._row_bases, dtype=torch.int64, device=self.dev)
         self.total_rows = int(sum(rows))
         ops.check_tbe_rows(self.total_rows, "DLRMTrainer (this rank's tables)")
         self.weights = torch.empty((max(self.total_rows, 1), D), dtype=torch.float32,
@@ -279,7 +286,7 @@ class DLRMTrainer:
         # run the embedding backward's per-table sort inside the lookup launch
         # (dlrm_tbe_forward_presort); False: the backward sorts itself
         self.tbe_presort = True
-        # (cfg.mlp_precision == "bf16", _segments16: a Linear is three 16-bit launches in
+        # (cfg.mlp_precision == "bf16", _build: a Linear is three 16-bit launches in
         # stream order and no launch role exists, so group_wgrad, full_last_wgrad, bot_sched,
         # fuse_bottom, dist_bottom_in_lookup, tbe_role, head_role, tbe_role_at and overlaps
         # below have no effect in that mode; tbe_presort, early_sort, fuse_gather and
@@ -329,14 +336,15 @@ class DLRMTrainer:
         self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count \
             if torch.cuda.is_available() else 256
         self.tbe_role_at = (0, 1)  # bottom-backward launches carrying pass 1 and pass 2
-        self._roles = []  # pending (role, phase) passes for the next _gemm launches
+        self._roles = []  # pending (role, phase) passes for the step's next GEMM launches
         self.gather_fused = False  # set by the last step
         self.bottom_fused = False  # set by the last step
         # device TBE error bits (ops.TBE_ERR_*): out-of-range indices are skipped by the
         # kernels and flagged here; check_errors() reads it (the step never syncs)
         self.tbe_error_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._colsum_ws: Optional[torch.Tensor] = None
-        self._head_ws: Optional[torch.Tensor] = None
+        self._head_step_ws: Optional[torch.Tensor] = None
+        self._rec_off = {}  # batch size -> the decode's private CSR offsets (_rec_offsets)
+        self._rec_scratch = None  # the full-batch decode scratch of record_batch
         self.step_count = 0
         # lr_mode "device": slot 0 the dense rate, 1 the embedding rate, 2 the dense rate / W
         # (the dense update of the W-rank schedule); None: host floats
@@ -358,7 +366,7 @@ class DLRMTrainer:
             t = self.local_tables[j]
             n = int(self.cfg.ln_emb[t])
             a = math.sqrt(1.0 / n)
-            view = self.weights[int(self.row_base[p].item()):int(self.row_base[p + 1].item())]
+            view = self.weights[self._rows(p)]
             if self.phys_kind[p] == 0:
                 ops.uniform_fill_(view, -a, a, seed * 1000003 + t)
             else:  # QR tables: uniform [sqrt(1/n), 1] (tricks/qr_embedding_bag.py:153-154)
@@ -381,11 +389,10 @@ class DLRMTrainer:
             if tables is not None:  # QR tables: (weight_q, weight_r) pairs
                 for p, j in enumerate(self.phys_src):
                     t = self.local_tables[j]
-                    s, e = int(self.row_base[p].item()), int(self.row_base[p + 1].item())
                     src = tables[t]
                     if self.phys_kind[p] != 0:
                         src = src[self.phys_kind[p] - 1]
-                    self.weights[s:e].copy_(torch.as_tensor(src))
+                    self.weights[self._rows(p)].copy_(torch.as_tensor(src))
 
     @classmethod
     def from_oracle(cls, cfg: TrainerConfig, ref, device="cuda:0", **kw):
@@ -404,22 +411,25 @@ class DLRMTrainer:
     def dense_state(self):
         return [(L.W[:, :L.K].detach().clone(), L.b.detach().clone()) for L in self.layers]
 
+    def _rows(self, p: int) -> slice:
+        """Physical table p's rows in the concatenated buffers."""
+        return slice(int(self._row_bases[p]), int(self._row_bases[p + 1]))
+
+    def _table_views(self, buf: torch.Tensor, t: int):
+        j = self.local_tables.index(t)
+        views = [buf[self._rows(p)] for p, jj in enumerate(self.phys_src) if jj == j]
+        return views[0] if len(views) == 1 else tuple(views)
+
     def table(self, t: int):
         """Local table t's weights (a (quotient, remainder) pair for a QR table)."""
-        j = self.local_tables.index(t)
-        views = [self.weights[int(self.row_base[p].item()):int(self.row_base[p + 1].item())]
-                 for p, jj in enumerate(self.phys_src) if jj == j]
-        return views[0] if len(views) == 1 else tuple(views)
+        return self._table_views(self.weights, t)
 
     def table_momentum(self, t: int):
         """RWSAdagrad row-wise momentum of local table t (a (quotient, remainder) pair for a
         QR table), the reference's optimizer state['momentum'] (optim/rwsadagrad.py:80-84)."""
         if self.momentum is None:
             raise ValueError("no row-wise momentum: optimizer is not rwsadagrad")
-        j = self.local_tables.index(t)
-        views = [self.momentum[int(self.row_base[p].item()):int(self.row_base[p + 1].item())]
-                 for p, jj in enumerate(self.phys_src) if jj == j]
-        return views[0] if len(views) == 1 else tuple(views)
+        return self._table_views(self.momentum, t)
 
     def dense_adagrad_state(self):
         """Per layer (sum of squared W gradients [N, K], of b [N]): the dense branch's
@@ -451,18 +461,6 @@ class DLRMTrainer:
             return lr, self.emb_lr, lr * (1.0 / self.world)
         s = self._lr_state
         return s.lr(0), s.lr(1), s.lr(2)
-
-    def _with_tick(self, fn):
-        """The step's first "gpu" segment: in lr_mode "device" it starts with the schedule's
-        tick, on the main stream before anything forks off it (the early sort's side stream
-        and the collectives wait for the main stream later, so they are ordered after it)."""
-        if self._lr_state is None:
-            return fn
-
-        def ticked():
-            ops.lr_schedule_tick(self._lr_state)
-            return fn()
-        return ticked
 
     def set_learning_rate(self, lr: float, emb_lr: Optional[float] = None) -> None:
         """New base learning rates (``emb_lr`` None: the embedding rate keeps following
@@ -605,9 +603,8 @@ class DLRMTrainer:
     def _rec_offsets(self, B: int) -> torch.Tensor:
         # the decode rewrites the L = 1 CSR offsets (arange); a private buffer keeps the
         # batch's own copy untouched while a graph may be reading it
-        t = self._rec_off.get(B) if hasattr(self, "_rec_off") else None
+        t = self._rec_off.get(B)
         if t is None:
-            self._rec_off = getattr(self, "_rec_off", {})
             t = self._rec_off[B] = torch.empty(self.T * B + 1, dtype=torch.int32, device=self.dev)
         return t
 
@@ -661,7 +658,7 @@ class DLRMTrainer:
             a[:, L.N] = 1.0
         bufs["R"][:, self.num_int] = 1.0
         wmax = max([L.Kp for L in self.layers] + [self.ldR])
-        # split-K workspaces: sized on the first step for this batch size (self._gemm grows
+        # split-K workspaces: sized on the first step for this batch size (the step's gemm grows
         # them before any capture), zeroed because the split-K tile tickets must start at 0
         # (the kernels leave them at 0).  They belong to this batch size: a hipGraph
         # captured for it keeps their addresses, and the main and side streams never share.
@@ -735,10 +732,23 @@ class DLRMTrainer:
         writes.  Optional side-stream overlaps (self.overlaps): "fwd" = bottom MLP || lookup,
         "bot" = bottom-MLP backward || embedding backward (joined inside the segment).
 
-        cfg.mlp_precision == "bf16": the list of _segments16 instead."""
-        if self.cfg.mlp_precision != "fp32":
-            return self._segments16(batch, profile)
+        cfg.mlp_precision == "bf16": the same list with the MLP layers on the 16-bit MFMA and,
+        for now, no launch role, no fused bottom chain and no overlap (_build)."""
+        return self._build(batch, profile)
+
+    def _build(self, batch: Batch, profile=None, predict=None):
+        """The segment list of the training step (segments) or, ``predict`` = (metrics,
+        precision), of the forward-only pass (predict_segments), from one set of pieces: the
+        context of this call first, then the pieces both lists use, the forward-only list,
+        the pieces of the backward and the step's four segment orders.
+
+        The precision of the MLP operands selects only the MLP closures (mlp_fwd, top_bwd,
+        bottom_bwd): "fp32" = grouped GEMM launches, "bf16" / "fp16" = one 16-bit launch per
+        layer and pass.  Every other piece is the same code for both."""
         cfg = self.cfg
+        train = predict is None
+        metrics, precision = (None, cfg.mlp_precision) if train else predict
+        fp32 = precision == "fp32"
         D = self.D
         Bl = batch.X.shape[0]
         B = Bl * self.world
@@ -750,19 +760,37 @@ class DLRMTrainer:
             raise ValueError(f"batch offsets hold {batch.offsets.numel()} entries, expected "
                              f"T_local*B+1 = {n_off} (B = {Bl} x {self.world} ranks)")
         bufs = self._buffers(Bl, B)
-        self._cur = bufs
         prof = profile or (lambda name: _NullCtx())
-        self._prof = prof
         fused_opt = self.grads is None  # single GPU SGD: updates fused into backward
         lr, elr, lr_w = self._rates()  # host floats, or the device slots (lr_mode "device")
         conc = self.concurrent and profile is None
         dist = self.distributed
-        c_fwd = conc and "fwd" in self.overlaps and not dist
-        c_bot = conc and "bot" in self.overlaps and not dist
         st = {}  # state shared by the segments (collective handles, pending reductions)
-        presort = self.tbe_presort
-        gather = presort and not dist and self._gather_applies(batch)
-        self.gather_fused = gather
+        # the forward-only pass runs dlrm_tbe_forward: nothing of the backward's sort
+        presort = train and self.tbe_presort
+        gather = (presort or not train) and not dist and self._gather_applies(batch)
+        # The 16-bit step has no launch role, no bottom chain in the lookup launch and no
+        # side-stream overlap (DESIGN.md §16 has the plan to give it them): they are switched
+        # off here, once, and the pieces below take the branches they take in an fp32 step
+        # with tbe_role, head_role, fuse_bottom and overlaps off.  The chain is an fp32
+        # kernel, so a 16-bit predict does not use it either; it keeps the "fwd" overlap.
+        plain = fp32 or not train
+        overlaps = self.overlaps if plain and not dist else ()
+        c_fwd = conc and "fwd" in overlaps
+        c_bot = conc and "bot" in overlaps
+        # the embedding update's passes, the head's finalize pass as roles of GEMM launches
+        tbe_role = (plain and self.tbe_role and profile is None
+                    and self.weights.dtype == torch.float32)
+        head_role = plain and self.head_role and profile is None and len(self.top) > 1
+        fuse_bottom = fp32 and self.fuse_bottom
+        if train:
+            self._cur = bufs
+            self.gather_fused = gather
+            ws, ws_keys = bufs, ("gemm_ws", "gemm_ws_side")
+        else:
+            # its own outputs and GEMM workspaces: it never touches self._cur, self._roles,
+            # gather_fused, bottom_fused or step_count
+            ws, ws_keys = self._predict_bufs(bufs), ("ws", "ws_side")
 
         def streams():
             s0 = torch.cuda.current_stream(self.dev)
@@ -771,55 +799,158 @@ class DLRMTrainer:
         def side_if(flag, s1):
             return torch.cuda.stream(s1) if flag else _NullCtx()
 
+        def gemm(problems, side=False):
+            """One grouped launch on this pass's workspace of the stream.  In a training step
+            a main-stream launch also carries the next pending pass of a deferred embedding
+            update or head (self._roles, set by the backward)."""
+            with prof("gemm"):
+                key = ws_keys[side]
+                need = ops.gemm_group_workspace_size(problems) if problems else 0
+                if need > ws[key].numel():  # first use of a new group shape (not in capture)
+                    ws[key] = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+                nxt = self._roles.pop(0) if train and not side and self._roles else None
+                role, phase = nxt if nxt is not None else (None, 0)
+                ops.gemm_group(problems, ws[key], self.dev, role=role, phase=phase)
+
+        def chain(**kw):
+            return self._bottom_chain(batch, bufs, **kw) if fuse_bottom else None
+
+        if fp32:
+            def mlp_fwd(L, h, out, side=False):
+                gemm([self._fwd(L, h, out)], side=side)
+        else:
+            # 16 bit: one launch, relu(r16(h[:, :K]) r16(W[:, :K])^T + b) -> out[:, :N], the
+            # operands rounded to nearest-even in flight from the fp32 tensors (no weight
+            # copy exists), fp32 accumulate; the constant-1 columns stay untouched
+            def mlp_fwd(L, h, out, side=False):
+                with prof("gemm"):
+                    ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True,
+                                         out=out[:, :L.N], dtype=precision)
+
         # the reference's profiler phase names (dlrm_s_pytorch.py:692-721, 171, 1923), so a
         # torch.profiler trace of this step lines up with one of the reference's
         emb_sizes = "-".join(str(int(cfg.ln_emb[t])) for t in self.local_tables)
 
-        def lookup():  # embeddings (full batch, local tables)
-            if dist:
-                self._roles = []  # first segment: no pass of an aborted step carries over
+        def lookup(bottom=None):
+            """Embeddings (full batch, local tables).  presort: the backward's per-table
+            sort runs inside the lookup launch (alone, when the interaction gathers the rows
+            itself); ``bottom``: the bottom MLP forward, a chain, as a further role of it."""
             with record_function("module::forward_pass::embedding_lookup", emb_sizes), \
                     prof("tbe_fwd"):
-                if self.T_local > 0:
-                    if "csr" not in st:
-                        st["csr"] = self._phys_csr(batch, B)
-                    idx, off = st["csr"]
-                    out = bufs["P"] if self.qr_active else bufs["E"]
-                if self.T_local > 0 and presort:
-                    # the backward's per-table sort runs inside the lookup launch (alone,
-                    # when the interaction gathers the rows itself); several GPUs: with the
-                    # bottom MLP forward as a third role (dist_bottom_in_lookup)
-                    chain = self._bottom_chain(batch, bufs) if dist and profile is None and \
-                        self.dist_bottom_in_lookup else None
-                    st["bottom_done"] = chain is not None
+                if self.T_local == 0:
+                    return
+                if "csr" not in st:
+                    st["csr"] = self._phys_csr(batch, B)
+                idx, off = st["csr"]
+                out = bufs["P"] if self.qr_active else bufs["E"]
+                if presort:
                     ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B, idx,
                                             off, self._ws_tbe(idx.numel()),
                                             batch.max_per_table, out=None if gather else out,
                                             out_batch_stride=out.stride(0),
-                                            error_flag=self.tbe_error_flag, bottom=chain,
+                                            error_flag=self.tbe_error_flag, bottom=bottom,
                                             lookup=not gather)
-                elif self.T_local > 0:
+                else:
                     ops.tbe_forward(self.weights, self.row_base, self.T_phys, B, idx, off,
                                     out=out, out_batch_stride=out.stride(0),
                                     error_flag=self.tbe_error_flag)
-                if self.T_local > 0 and self.qr_active:
-                    self._qr_combine(bufs, B)
+                if self.qr_active:
+                    ops.qr_pool_combine_forward(cfg.qr_operation, self.T_local, B, D,
+                                                self._qr_pq, self._qr_pr, bufs["P"], bufs["E"])
+
+        # the bottom MLP as one row-block chain launch of its own (activations in LDS between
+        # layers, mlp_rows.hpp): several GPUs, while the all-to-all is in flight, and predict
+        own_chain = not train or (dist and profile is None)
 
         def bottom_fwd():
-            h = batch.X
             if st.pop("bottom_done", False):  # ran inside the lookup launch
                 return _EMPTY
             with record_function("module::forward_pass::bottom_mlp"):
-                if dist and profile is None:
-                    # several GPUs: the bottom MLP as one row-block chain launch (activations
-                    # in LDS between layers, mlp_rows.hpp) while the all-to-all is in flight
-                    chain = self._bottom_chain(batch, bufs, sort_wgs=0, standalone=True)
-                    if chain is not None:
-                        ops.mlp_chain_forward(chain, self.dev)
-                        return
+                c = chain(sort_wgs=0, standalone=True) if own_chain else None
+                if c is not None:
+                    ops.mlp_chain_forward(c, self.dev)
+                    return
+                h = batch.X
                 for L, out in zip(self.bot, bufs["bot_act"]):
-                    self._gemm([self._fwd(L, h, out)], side=c_fwd)
+                    mlp_fwd(L, h, out, side=c_fwd)
                     h = out
+
+        def beside_bottom(look):
+            """One GPU: ``look`` (or nothing) on the main stream, then the bottom MLP - with
+            the "fwd" overlap beside it, on the side stream."""
+            s0, s1 = streams()
+            if c_fwd:
+                s1.wait_stream(s0)
+            if look is not None:
+                look()
+            with side_if(c_fwd, s1):
+                bottom_fwd()
+            if c_fwd:
+                s0.wait_stream(s1)
+
+        def interaction_fwd():
+            x, feats = self._features(bufs, Bl)
+            with record_function("module::forward_pass::interaction"), prof("interaction_fwd"):
+                if gather:  # one-hot lookup fused: rows read straight from the tables
+                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
+                                                cfg.arch_interaction_itself, out=bufs["R"],
+                                                error_flag=self.tbe_error_flag)
+                else:
+                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
+                                         cfg.arch_interaction_itself, out=bufs["R"])
+            return x, feats
+
+        def top_fwd():  # the top MLP below the head
+            h = bufs["R"]
+            for L, out in zip(self.top[:-1], bufs["top_act"]):
+                mlp_fwd(L, h, out)
+                h = out
+            return h
+
+        def wait(key):
+            return lambda: st.pop(key).wait()
+
+        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
+        last = self.top[-1]
+
+        if not train:
+            def lookup_only():  # no launch when the interaction gathers the rows itself
+                if self.T_local == 0 or gather:
+                    return _EMPTY
+                st.pop("csr", None)  # QR: every run expands the batch's current contents
+                lookup()
+
+            def score():
+                interaction_fwd()
+                with record_function("module::forward_pass::top_mlp"):
+                    h = top_fwd()
+                    ops.head_predict(h[:, :last.Kp], last.W[0, :last.Kp], cfg.loss_threshold,
+                                     prob=ws["prob"],
+                                     target=batch.target if metrics is not None else None,
+                                     state=metrics)
+
+            if not dist:
+                return [("gpu", lambda: beside_bottom(lookup_only)), ("gpu", score)]
+            return [
+                ("gpu", lookup_only),
+                ("a2a", a2a_fwd),
+                ("gpu", bottom_fwd),
+                ("a2a", wait("a2a")),
+                ("gpu", score),
+            ]
+
+        def first(fn):
+            """The step's first segment.  A launch role deferred by an aborted step (raw
+            pointers of that step) must never ride on this step's launches; and in lr_mode
+            "device" the step starts with the schedule's tick, on the main stream before
+            anything forks off it (the early sort's side stream and the collectives wait for
+            the main stream later, so they are ordered after it)."""
+            def run():
+                self._roles = []
+                if self._lr_state is not None:
+                    ops.lr_schedule_tick(self._lr_state)
+                return fn()
+            return run
 
         def early_sort():  # the backward's sort on the side stream, beside the forward
             s0, s1 = streams()
@@ -832,196 +963,218 @@ class DLRMTrainer:
             st["sorted"] = s1
 
         def fwd_single():  # one GPU: bottom MLP || lookup
-            # first segment of the step: a launch role deferred by an aborted step (raw
-            # pointers of that step) must never ride on this step's launches
-            self._roles = []
             es = (self.early_sort and conc and self.T_local > 0 and presort
                   and not 0 < batch.max_per_table <= ops.TBE_PRESORT_SEG_CAP)
-            if es and self.early_sort != 2:  # 2: forked after the lookup launch instead
+            late = es and self.early_sort == 2  # 2: forked after the lookup launch instead
+            if es and not late:
                 early_sort()
-            chain = self._bottom_chain(batch, bufs) if presort and not c_fwd else None
-            self.bottom_fused = chain is not None
-            if chain is not None:
-                # the bottom MLP forward runs as a role of the lookup launch
-                with record_function("module::forward_pass::embedding_lookup", emb_sizes), \
-                        record_function("module::forward_pass::bottom_mlp"), prof("tbe_fwd"):
-                    if "csr" not in st:
-                        st["csr"] = self._phys_csr(batch, B)
-                    idx, off = st["csr"]
-                    out = None if gather else bufs["P"] if self.qr_active else bufs["E"]
-                    ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B, idx,
-                                            off, self._ws_tbe(idx.numel()),
-                                            batch.max_per_table, out=out,
-                                            out_batch_stride=None if out is None else
-                                            out.stride(0),
-                                            error_flag=self.tbe_error_flag, bottom=chain,
-                                            lookup=not gather)
-                    if self.qr_active:
-                        self._qr_combine(bufs, B)
-                if es and self.early_sort == 2:
-                    early_sort()
-                return
-            s0, s1 = streams()
-            if es and self.early_sort == 2:
+            c = chain() if presort and not c_fwd else None
+            self.bottom_fused = c is not None
+            if c is not None:  # the bottom MLP forward runs as a role of the lookup launch
+                with record_function("module::forward_pass::bottom_mlp"):
+                    lookup(c)
+            elif late:
                 lookup()
+            if late:
                 early_sort()
-                s0, s1 = streams()
-            if c_fwd:
-                s1.wait_stream(s0)
-            if not (es and self.early_sort == 2):
-                lookup()
-            with side_if(c_fwd, s1):
-                bottom_fwd()
-            if c_fwd:
-                s0.wait_stream(s1)
+            if c is None:
+                beside_bottom(None if late else lookup)
 
-        def top():  # interaction, top MLP, head, top backward
-            x, feats = self._features(bufs, Bl)
-            with record_function("module::forward_pass::interaction"), prof("interaction_fwd"):
-                if gather:  # one-hot lookup fused: rows read straight from the tables
-                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
-                                                cfg.arch_interaction_itself, out=bufs["R"],
-                                                error_flag=self.tbe_error_flag)
-                else:
-                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
-                                         cfg.arch_interaction_itself, out=bufs["R"])
-            h = bufs["R"]
-            with record_function("module::forward_pass::top_mlp"):
-                for L, out in zip(self.top[:-1], bufs["top_act"]):
-                    self._gemm([self._fwd(L, h, out)])
-                    h = out
-            last = self.top[-1]
-            # head: last layer + sigmoid + loss + dz + input grad + [dw | db] (bias folded:
-            # [h | 1] . [w | b]) in two launches; the update follows every read of w
-            G = bufs["g"]
-            gi = 0
-            gview = G[gi][:, :last.Kp]
-            # the head's second launch (column sums + update or gradient + mean loss) rides
-            # on the top-MLP backward's first GEMM launch (dlrm_head_step_defer)
-            head_role = self.head_role and profile is None and len(self.top) > 1
+        def lookup_dist():
+            # several GPUs: the bottom MLP forward as a role of the lookup launch too
+            c = chain() if presort and profile is None and self.dist_bottom_in_lookup else None
+            st["bottom_done"] = c is not None
+            lookup(c)
+
+        def head(h):
+            """Last layer + sigmoid + loss + dz + input grad + [dw | db] (bias folded:
+            [h | 1] . [w | b]) in two launches; the update follows every read of w.  Returns
+            the gradient of the head's input.  head_role: the second launch (column sums +
+            update or gradient + mean loss) rides on the top-MLP backward's first GEMM launch
+            (dlrm_head_step_defer)."""
+            g = bufs["g"][0][:, :last.Kp]
             with record_function("## Loss Compute ##"), prof("head"):
                 r = ops.head_step(h[:, :last.Kp], last.W[0, :last.Kp], batch.target,
                                   cfg.loss_function, cfg.loss_threshold, 1.0, prob=bufs["prob"],
-                                  dz=bufs["dz"], loss_out=bufs["loss"], dX=gview,
+                                  dz=bufs["dz"], loss_out=bufs["loss"], dX=g,
                                   relu_mask=len(self.top) > 1,
                                   dw=None if fused_opt else last.gW[0, :last.Kp],
                                   lr=lr if fused_opt else 0.0,
                                   workspace=self._ws_head_step(Bl, last.Kp), defer=head_role)
                 if head_role:
                     self._roles = [x for x in self._roles if x is not None] + [(r, 4)]
-            g = gview
-            rq = []  # reduce jobs riding on the next launch; G rotates over three buffers
-            bwd = record_function("## Backward ##")
-            bwd.__enter__()
-            for li in range(len(self.top) - 2, -1, -1):
-                L = self.top[li]
-                inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
-                gn = (gi + 1) % 3
-                dg = self._dgrad(L, g, inp if li > 0 else None, G[gn])
-                # several GPUs: the top bucket is all-reduced right after this loop, so its
-                # last wgrad reduces its K split inside its own launch
-                w, r = self._wg(L, g, inp, fused_opt, lr, ("top", li), full=dist and li == 0)
-                if r is not None and self.group_wgrad:
-                    # the split wgrad only writes partials (its update rides on the next
-                    # launch's reduce job), so it may run beside the dgrad reading W
-                    self._gemm([dg, w] + rq)
-                    rq = [r]
-                elif r is None and not fused_opt:
-                    # the wgrad writes the gradient bucket, not W: beside the dgrad
-                    self._gemm([dg, w] + rq)
-                    rq = []
-                elif r is not None:
-                    # a split wgrad kept out of the dgrad's launch (group_wgrad off): its
-                    # partials in a launch of their own, its reduce job on the next one
-                    self._gemm([dg] + rq)
-                    self._gemm([w])
-                    rq = [r]
-                else:
-                    # an unsplit wgrad updates W_l in its epilogue: it rides on the NEXT
-                    # launch (dgrad of layer l-1 reads W_{l-1}, not W_l; its g_l buffer
-                    # is not overwritten there: G rotates over three)
-                    self._gemm([dg] + rq)
-                    rq = [w]
-                g, gi = G[gn], gn
-            bwd.__exit__(None, None, None)
-            st.update(rq=rq, x=x, feats=feats, g=g)
+            return g
+
+        # The MLP backward, from the head's input gradient down.  Both forms walk the layers
+        # from the top; the gradient rotates over three buffers (bufs["g"]; the bottom MLP's
+        # over bufs["gb"]); the top MLP's first layer has no ReLU mask (its input is the
+        # interaction) and the bottom MLP's first layer no data gradient at all.
+        if fp32:
+            def top_bwd(g):
+                """Returns the gradient of the interaction's output; the reduce jobs still
+                to ride on a launch go to st["rq"]."""
+                G, gi = bufs["g"], 0
+                rq = []  # reduce jobs riding on the next launch
+                for li in range(len(self.top) - 2, -1, -1):
+                    L = self.top[li]
+                    inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
+                    gn = (gi + 1) % 3
+                    dg = self._dgrad(L, g, inp if li > 0 else None, G[gn])
+                    # several GPUs: the top bucket is all-reduced right after this loop, so
+                    # its last wgrad reduces its K split inside its own launch
+                    w, r = self._wg(L, g, inp, fused_opt, lr, ("top", li),
+                                    full=dist and li == 0)
+                    if r is not None and self.group_wgrad:
+                        # the split wgrad only writes partials (its update rides on the next
+                        # launch's reduce job), so it may run beside the dgrad reading W
+                        gemm([dg, w] + rq)
+                        rq = [r]
+                    elif r is None and not fused_opt:
+                        # the wgrad writes the gradient bucket, not W: beside the dgrad
+                        gemm([dg, w] + rq)
+                        rq = []
+                    elif r is not None:
+                        # a split wgrad kept out of the dgrad's launch (group_wgrad off): its
+                        # partials in a launch of their own, its reduce job on the next one
+                        gemm([dg] + rq)
+                        gemm([w])
+                        rq = [r]
+                    else:
+                        # an unsplit wgrad updates W_l in its epilogue: it rides on the NEXT
+                        # launch (dgrad of layer l-1 reads W_{l-1}, not W_l; its g_l buffer
+                        # is not overwritten there: G rotates over three)
+                        gemm([dg] + rq)
+                        rq = [w]
+                    g, gi = G[gn], gn
+                st["rq"] = rq
+                return g
+
+            def bottom_bwd_full():
+                """Bottom-MLP backward with in-launch split-K wgrads (FULL, SGD fused): the
+                wgrad of layer l rides in the launch of dgrad(l-1), which does not read W_l,
+                and the last launch holds the two lowest wgrads - n_bot launches, no trailing
+                REDUCE.  dgrad(l) writes g_{l-1} into buffer l % 3: the wgrad it shares a
+                launch with reads g_{l+1} from buffer (l+2) % 3."""
+                rq = st.pop("rq")
+                g = bufs["gx"]
+                pending = []
+                for li in range(self.n_bot - 1, -1, -1):
+                    L = self.bot[li]
+                    inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
+                    w = self._wgrad(L, g, inp, fused_opt, lr)
+                    if li > 0:
+                        out = bufs["gb"][li % 3]
+                        gemm([self._dgrad(L, g, inp, out)] + pending + rq)
+                        rq, pending, g = [], [w], out
+                    else:
+                        gemm(pending + [w] + rq)
+
+            def bottom_bwd(hold_last=False):
+                """hold_last: the last launch's problems go to st["bot_last"] instead of
+                being launched (several GPUs: it then carries the embedding update's first
+                pass once the reverse all-to-all has landed)."""
+                sched = self.bot_sched
+                if sched == "auto":
+                    sched = "full" if Bl <= 128 else "partial"
+                if sched == "full" and not c_bot and fused_opt:
+                    return bottom_bwd_full()
+                rq = st.pop("rq")
+                g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
+                bg = [bufs["gb"][0], bufs["gb"][1]]
+                launches = []
+                for li in range(self.n_bot - 1, -1, -1):
+                    L = self.bot[li]
+                    inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
+                    w, r = self._wg(L, g, inp, fused_opt, lr, ("bot", li), last=li == 0)
+                    if li > 0 and r is not None and self.group_wgrad:
+                        launches.append([self._dgrad(L, g, inp, bg[li % 2]), w] + rq)
+                    elif li > 0 and r is None and not fused_opt:
+                        # the wgrad writes the gradient bucket, not W: beside the dgrad
+                        launches.append([self._dgrad(L, g, inp, bg[li % 2]), w] + rq)
+                    else:
+                        if li > 0:
+                            launches.append([self._dgrad(L, g, inp, bg[li % 2])] + rq)
+                            rq = []
+                        launches.append([w] + rq)
+                    rq = [r] if r is not None else []
+                    if li > 0:
+                        g = bg[li % 2]
+                if rq:
+                    launches.append(rq)
+                if hold_last:
+                    st["bot_last"] = launches.pop()
+                for probs in launches:
+                    gemm(probs, side=c_bot)
+        else:
+            # 16 bit (bf16): a layer is two launches in stream order, ops.linear16_dgrad
+            # (mask = the layer's input activation) and then ops.linear16_wgrad over the
+            # K + 1 columns [inp | 1] -> [W | b] (the constant-1 column yields
+            # db = sum_m r16(g)), SGD-fused into W on one GPU with SGD, else stored into the
+            # gradient bucket.  Stream order puts a layer's update after the dgrad that
+            # reads its W.  group_wgrad, full_last_wgrad and bot_sched have no effect here.
+            def dgrad16(L, g, inp, out):
+                with prof("gemm"):
+                    ops.linear16_dgrad(g[:, :L.N], L.W[:, :L.K],
+                                       None if inp is None else inp[:, :L.K], out=out[:, :L.K],
+                                       dtype=precision)
+
+            def wgrad16(L, g, inp):
+                C = L.W if fused_opt else L.gW
+                with prof("gemm"):
+                    ops.linear16_wgrad(g[:, :L.N], inp[:, :L.K + 1], C[:, :L.K + 1],
+                                       lr=lr if fused_opt else None, dtype=precision,
+                                       workspace=self._ws_wgrad16(bufs, Bl, L.N, L.K + 1))
+
+            def top_bwd(g):
+                G, gi = bufs["g"], 0
+                for li in range(len(self.top) - 2, -1, -1):
+                    L = self.top[li]
+                    inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
+                    gn = (gi + 1) % 3
+                    dgrad16(L, g, inp if li > 0 else None, G[gn])
+                    wgrad16(L, g, inp)
+                    g, gi = G[gn], gn
+                return g
+
+            def bottom_bwd():
+                g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
+                for li in range(self.n_bot - 1, -1, -1):
+                    L = self.bot[li]
+                    inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
+                    if li > 0:
+                        dgrad16(L, g, inp, bufs["gb"][li % 2])
+                    wgrad16(L, g, inp)
+                    if li > 0:
+                        g = bufs["gb"][li % 2]
+
+        def top():  # interaction, top MLP, head, top backward
+            x, feats = interaction_fwd()
+            with record_function("module::forward_pass::top_mlp"):
+                h = top_fwd()
+            g = head(h)
+            with record_function("## Backward ##"):
+                g = top_bwd(g)
+            st.update(x=x, feats=feats, g=g)
 
         def interaction_bwd():
             x, feats, g = st.pop("x"), st.pop("feats"), st.pop("g")
-            bwd = record_function("## Backward ##")
-            bwd.__enter__()
-            _, gfeats = self._features(bufs, Bl, grad=True)
-            with prof("interaction_bwd"):  # + the backward of the bottom MLP's last ReLU
-                if gather:  # rows re-gathered (the embedding update comes later)
-                    ops.interact_backward_gather(x, self.weights, self.row_base, batch.indices,
-                                                 g[:, :self.num_int], cfg.arch_interaction_itself,
-                                                 grad_x=bufs["gx"], grad_ly=gfeats, relu_x=True)
-                else:
-                    ops.interact_backward(cfg.arch_interaction_op, x, feats, g[:, :self.num_int],
-                                          cfg.arch_interaction_itself, grad_x=bufs["gx"],
-                                          grad_ly=gfeats, relu_x=True)
-            bwd.__exit__(None, None, None)
+            with record_function("## Backward ##"):
+                _, gfeats = self._features(bufs, Bl, grad=True)
+                with prof("interaction_bwd"):  # + the backward of the bottom MLP's last ReLU
+                    if gather:  # rows re-gathered (the embedding update comes later)
+                        ops.interact_backward_gather(
+                            x, self.weights, self.row_base, batch.indices, g[:, :self.num_int],
+                            cfg.arch_interaction_itself, grad_x=bufs["gx"], grad_ly=gfeats,
+                            relu_x=True)
+                    else:
+                        ops.interact_backward(
+                            cfg.arch_interaction_op, x, feats, g[:, :self.num_int],
+                            cfg.arch_interaction_itself, grad_x=bufs["gx"], grad_ly=gfeats,
+                            relu_x=True)
 
         def middle():  # interaction, top MLP, head, top backward, interaction backward
             top()
             interaction_bwd()
-
-        def bottom_bwd_full():
-            """Bottom-MLP backward with in-launch split-K wgrads (FULL, SGD fused): the
-            wgrad of layer l rides in the launch of dgrad(l-1), which does not read W_l,
-            and the last launch holds the two lowest wgrads - n_bot launches, no trailing
-            REDUCE.  dgrad(l) writes g_{l-1} into buffer l % 3: the wgrad it shares a launch
-            with reads g_{l+1} from buffer (l+2) % 3."""
-            rq = st.pop("rq")
-            g = bufs["gx"]
-            pending = []
-            for li in range(self.n_bot - 1, -1, -1):
-                L = self.bot[li]
-                inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
-                w = self._wgrad(L, g, inp, fused_opt, lr)
-                if li > 0:
-                    out = bufs["gb"][li % 3]
-                    self._gemm([self._dgrad(L, g, inp, out)] + pending + rq)
-                    rq, pending, g = [], [w], out
-                else:
-                    self._gemm(pending + [w] + rq)
-
-        def bottom_bwd(s1=None, hold_last=False):
-            """hold_last: the last launch's problems go to st["bot_last"] instead of being
-            launched (several GPUs: it then carries the embedding update's first pass once
-            the reverse all-to-all has landed)."""
-            sched = self.bot_sched
-            if sched == "auto":
-                sched = "full" if Bl <= 128 else "partial"
-            if sched == "full" and not c_bot and fused_opt:
-                return bottom_bwd_full()
-            rq = st.pop("rq")
-            g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
-            bg = [bufs["gb"][0], bufs["gb"][1]]
-            launches = []
-            for li in range(self.n_bot - 1, -1, -1):
-                L = self.bot[li]
-                inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
-                w, r = self._wg(L, g, inp, fused_opt, lr, ("bot", li), last=li == 0)
-                if li > 0 and r is not None and self.group_wgrad:
-                    launches.append([self._dgrad(L, g, inp, bg[li % 2]), w] + rq)
-                elif li > 0 and r is None and not fused_opt:
-                    # the wgrad writes the gradient bucket, not W: beside the dgrad
-                    launches.append([self._dgrad(L, g, inp, bg[li % 2]), w] + rq)
-                else:
-                    if li > 0:
-                        launches.append([self._dgrad(L, g, inp, bg[li % 2])] + rq)
-                        rq = []
-                    launches.append([w] + rq)
-                rq = [r] if r is not None else []
-                if li > 0:
-                    g = bg[li % 2]
-            if rq:
-                launches.append(rq)
-            if hold_last:
-                st["bot_last"] = launches.pop()
-            for probs in launches:
-                self._gemm(probs, side=c_bot)
 
         def emb_bwd(defer=False):  # embedding backward + fused update
             """defer=True: the update's two passes are returned as a role for the next two
@@ -1052,16 +1205,14 @@ class DLRMTrainer:
         def backward_single():  # one GPU: bottom backward || embedding backward
             s0, s1 = streams()
             if c_bot:
-                rq = st["rq"]
-                if rq:
-                    self._gemm(rq)
+                if st["rq"]:
+                    gemm(st["rq"])
                 st["rq"] = []
                 s1.wait_stream(s0)
             # the embedding update's two HBM-bound passes ride as extra workgroups on the
             # first two (MFMA-bound) bottom-backward launches: overlap with no cross-queue
             # dependency (dlrm_tbe_backward_defer / dlrm_gemm_f32_group_role)
-            deferred = (self.tbe_role and not c_bot and self.T_local > 0 and profile is None
-                        and self.weights.dtype == torch.float32)
+            deferred = tbe_role and not c_bot and self.T_local > 0
             if deferred:
                 a, b = self._check_role_at(self.tbe_role_at)
                 role = emb_bwd(defer=True)
@@ -1074,7 +1225,7 @@ class DLRMTrainer:
                 if self._roles[0] is None:
                     self._roles.pop(0)
                 else:
-                    self._gemm([])
+                    gemm([])
             if not deferred:
                 emb_bwd()
             if c_bot:
@@ -1082,7 +1233,6 @@ class DLRMTrainer:
 
         def dense_update():
             with record_function("## Backward ##"), prof("dense_update"):
-                scale = 1.0 / self.world
                 if cfg.optimizer == "sgd" and st.pop("top_updated", False):
                     # the top bucket's update rode on the embedding update's second pass
                     nb = self.n_bot_params
@@ -1091,18 +1241,16 @@ class DLRMTrainer:
                     ops.sgd_update(self.params, self.grads, lr_w)
                 else:  # the 1/W folded into the update (one pass over the bucket)
                     ops.adagrad_update(self.params, self.grads, self.adagrad_sum, lr,
-                                       cfg.adagrad_eps, grad_scale=scale)
+                                       cfg.adagrad_eps, grad_scale=1.0 / self.world)
 
         def done():
             self.step_count += 1
 
         if not dist:
-            segs = [("gpu", self._with_tick(fwd_single)), ("gpu", middle),
-                    ("gpu", backward_single)]
+            segs = [("gpu", first(fwd_single)), ("gpu", middle), ("gpu", backward_single)]
             if not fused_opt:
                 segs.append(("gpu", dense_update))
             return segs + [("host", done)]
-        lookup = self._with_tick(lookup)
         # multi GPU (distributed_forward, dlrm_s_pytorch.py:686-730; DDP :1626-1633):
         #  * the pooled-embedding all-to-all overlaps the bottom MLP (one chain launch);
         #  * the top MLP's gradient bucket is all-reduced as soon as the top backward is
@@ -1118,27 +1266,15 @@ class DLRMTrainer:
                 st["ar_" + bucket] = self.comm.allreduce(g)
             return start
 
-        def wait(key):
-            return lambda: st.pop(key).wait()
-
-        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
         a2a_bwd = lambda: st.__setitem__("a2a", self._alltoall_bwd(bufs, Bl))  # noqa: E731
-        # the embedding update's two passes as launch roles (as on one GPU): the first on
-        # the bottom backward's last launch, held back until the reverse all-to-all has
-        # landed; the second on a launch that also applies the top bucket's SGD update.
-        # The choice must not depend on the rank (T_local): every rank issues the same
-        # collectives in the same order (a rank without tables just carries no role)
-        roles_dist = self.tbe_role and profile is None and self.weights.dtype == torch.float32
-
-        def bottom_head():
-            bottom_bwd(hold_last=roles_dist)
+        bwd = lambda fn: record_function("## Backward ##")(fn)  # noqa: E731
 
         def bottom_tail():  # after All2All_Wait: the update's passes ride on GEMM launches
             role = emb_bwd(defer=True)
             if role is not None:
                 self._roles = [(role, 1)]
                 st["emb_role"] = role
-            self._gemm(st.pop("bot_last"))
+            gemm(st.pop("bot_last"))
             self._roles = []
 
         def emb_pass2():
@@ -1151,7 +1287,7 @@ class DLRMTrainer:
                 jobs = [ops.sgd_job(self.params[nb:], self.grads[nb:], lr_w)]
                 st["top_updated"] = True
             self._roles = [(role, 2)]
-            self._gemm(jobs)
+            gemm(jobs)
             self._roles = []
 
         # RCCL: the all-reduces capture into hipGraphs, the all-to-alls do not (DESIGN.md §8:
@@ -1159,323 +1295,61 @@ class DLRMTrainer:
         # stack).  Each all-reduce is waited in the graph that issues it, so the step is FOUR
         # graphs around the two eager all-to-alls: the top bucket overlaps the bottom
         # backward and the reverse all-to-all, the bottom bucket the embedding update's
-        # second pass.  gloo (host-staged, synchronous) runs the same order eagerly.
-        if roles_dist:
-            return [
-                ("gpu", lookup),
-                ("a2a", a2a_fwd),
-                ("gpu", bottom_fwd),
-                ("a2a", wait("a2a")),  # All2All_Wait (extend_distributed.py:489)
-                ("gpu", top),
-                ("gpu", interaction_bwd),
-                ("a2a", a2a_bwd),
-                ("ar", ar("top")),
-                ("gpu", record_function("## Backward ##")(bottom_head)),
-                ("ar", wait("ar_top")),
-                ("a2a", wait("a2a")),
-                ("gpu", record_function("## Backward ##")(bottom_tail)),
-                ("ar", ar("bot")),
-                ("gpu", record_function("## Backward ##")(emb_pass2)),
-                ("ar", wait("ar_bot")),
-                ("gpu", dense_update),
-                ("host", done),
-            ]
-        if getattr(self.comm, "capture_ar", False):
-            return [
-                ("gpu", lookup),
-                ("a2a", a2a_fwd),
-                ("gpu", bottom_fwd),
-                ("a2a", wait("a2a")),  # All2All_Wait (extend_distributed.py:489)
-                ("gpu", top),
-                ("gpu", interaction_bwd),
-                ("a2a", a2a_bwd),
-                ("ar", ar("top")),
-                ("gpu", record_function("## Backward ##")(bottom_bwd)),
-                ("ar", wait("ar_top")),
-                ("a2a", wait("a2a")),
-                ("ar", ar("bot")),
-                ("gpu", record_function("## Backward ##")(emb_bwd)),
-                ("ar", wait("ar_bot")),
-                ("gpu", dense_update),
-                ("host", done),
-            ]
-        return [
-            ("gpu", lookup),
+        # second pass.  gloo (host-staged, synchronous) runs the same order eagerly, with
+        # the top bucket's all-reduce started right after the top backward.
+        forward = [
+            ("gpu", first(lookup_dist)),
             ("a2a", a2a_fwd),
             ("gpu", bottom_fwd),
             ("a2a", wait("a2a")),  # All2All_Wait (extend_distributed.py:489)
             ("gpu", top),
+        ]
+        if tbe_role:
+            # the embedding update's two passes as launch roles (as on one GPU): the first on
+            # the bottom backward's last launch, held back until the reverse all-to-all has
+            # landed; the second on a launch that also applies the top bucket's SGD update.
+            # The choice must not depend on the rank (T_local): every rank issues the same
+            # collectives in the same order (a rank without tables just carries no role)
+            return forward + [
+                ("gpu", interaction_bwd),
+                ("a2a", a2a_bwd),
+                ("ar", ar("top")),
+                ("gpu", bwd(lambda: bottom_bwd(hold_last=True))),
+                ("ar", wait("ar_top")),
+                ("a2a", wait("a2a")),
+                ("gpu", bwd(bottom_tail)),
+                ("ar", ar("bot")),
+                ("gpu", bwd(emb_pass2)),
+                ("ar", wait("ar_bot")),
+                ("gpu", dense_update),
+                ("host", done),
+            ]
+        if getattr(self.comm, "capture_ar", False):
+            return forward + [
+                ("gpu", interaction_bwd),
+                ("a2a", a2a_bwd),
+                ("ar", ar("top")),
+                ("gpu", bwd(bottom_bwd)),
+                ("ar", wait("ar_top")),
+                ("a2a", wait("a2a")),
+                ("ar", ar("bot")),
+                ("gpu", bwd(emb_bwd)),
+                ("ar", wait("ar_bot")),
+                ("gpu", dense_update),
+                ("host", done),
+            ]
+        return forward + [
             ("ar", ar("top")),
             ("gpu", interaction_bwd),
             ("a2a", a2a_bwd),
-            ("gpu", record_function("## Backward ##")(bottom_bwd)),
+            ("gpu", bwd(bottom_bwd)),
             ("ar", ar("bot")),
             ("a2a", wait("a2a")),
-            ("gpu", record_function("## Backward ##")(emb_bwd)),
+            ("gpu", bwd(emb_bwd)),
             ("ar", wait("ar_top")),
             ("ar", wait("ar_bot")),
             ("gpu", dense_update),
             ("host", done),
-        ]
-
-
-    def _segments16(self, batch: Batch, profile=None):
-        """The mixed-precision step (cfg.mlp_precision == "bf16") in the form of segments().
-
-        Every bottom- and top-MLP Linear below the head is three launches on the 16-bit MFMA,
-        operands rounded to nearest-even from the fp32 tensors in flight, fp32 accumulate:
-          forward  ops.linear16_forward(h[:, :K], W[:, :K], b, ReLU) -> out[:, :N], as
-                   predict_segments issues it (the constant-1 columns stay untouched);
-          backward, layer by layer from the top, in stream order:
-                   ops.linear16_dgrad (mask = the layer's input activation; none for the top
-                   MLP's first layer, no dgrad at all for the bottom MLP's first layer), then
-                   ops.linear16_wgrad over the K + 1 columns [inp | 1] -> [W | b] (the
-                   constant-1 column yields db = sum_m r16(g)), SGD-fused into W on one GPU
-                   with SGD, else stored into the gradient bucket.  Stream order puts a
-                   layer's update after the dgrad that reads its W.
-        The lookup (with its sort role, early_sort, fuse_gather), the interaction, the head
-        (fp32 K -> 1 layer and its gradients), the interaction backward, the embedding
-        backward, the QR combine, the all-to-alls, the all-reduces and the dense update are
-        the fp32 path's calls.  No launch role exists in this mode (self._roles stays empty,
-        the embedding backward and the head run undeferred), the fused bottom chain is not
-        used, and the side stream carries only the early sort: tbe_role, head_role,
-        fuse_bottom, dist_bottom_in_lookup, bot_sched, group_wgrad, full_last_wgrad and
-        overlaps have no effect."""
-        cfg = self.cfg
-        dt = cfg.mlp_precision
-        Bl = batch.X.shape[0]
-        B = Bl * self.world
-        n_off = self.T_local * B + 1
-        if self.T_local > 0 and batch.offsets.numel() != n_off:
-            raise ValueError(f"batch offsets hold {batch.offsets.numel()} entries, expected "
-                             f"T_local*B+1 = {n_off} (B = {Bl} x {self.world} ranks)")
-        bufs = self._buffers(Bl, B)
-        self._cur = bufs
-        prof = profile or (lambda name: _NullCtx())
-        self._prof = prof
-        fused_opt = self.grads is None
-        lr, elr, lr_w = self._rates()  # host floats, or the device slots (lr_mode "device")
-        conc = self.concurrent and profile is None
-        dist = self.distributed
-        st = {}
-        presort = self.tbe_presort
-        gather = presort and not dist and self._gather_applies(batch)
-        self.gather_fused = gather
-        self.bottom_fused = False
-        emb_sizes = "-".join(str(int(cfg.ln_emb[t])) for t in self.local_tables)
-
-        def fwd16(L, h, out):
-            with prof("gemm"):
-                ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True, out=out[:, :L.N],
-                                     dtype=dt)
-
-        def dgrad16(L, g, inp, out):
-            with prof("gemm"):
-                ops.linear16_dgrad(g[:, :L.N], L.W[:, :L.K],
-                                   None if inp is None else inp[:, :L.K], out=out[:, :L.K],
-                                   dtype=dt)
-
-        def wgrad16(L, g, inp):
-            C = L.W if fused_opt else L.gW
-            with prof("gemm"):
-                ops.linear16_wgrad(g[:, :L.N], inp[:, :L.K + 1], C[:, :L.K + 1],
-                                   lr=lr if fused_opt else None, dtype=dt,
-                                   workspace=self._ws_wgrad16(bufs, Bl, L.N, L.K + 1))
-
-        def lookup():
-            self._roles = []
-            with record_function("module::forward_pass::embedding_lookup", emb_sizes), \
-                    prof("tbe_fwd"):
-                if self.T_local == 0:
-                    return
-                if "csr" not in st:
-                    st["csr"] = self._phys_csr(batch, B)
-                idx, off = st["csr"]
-                out = bufs["P"] if self.qr_active else bufs["E"]
-                if presort:
-                    ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B, idx,
-                                            off, self._ws_tbe(idx.numel()),
-                                            batch.max_per_table, out=None if gather else out,
-                                            out_batch_stride=out.stride(0),
-                                            error_flag=self.tbe_error_flag, bottom=None,
-                                            lookup=not gather)
-                else:
-                    ops.tbe_forward(self.weights, self.row_base, self.T_phys, B, idx, off,
-                                    out=out, out_batch_stride=out.stride(0),
-                                    error_flag=self.tbe_error_flag)
-                if self.qr_active:
-                    self._qr_combine(bufs, B)
-
-        def bottom_fwd():
-            h = batch.X
-            with record_function("module::forward_pass::bottom_mlp"):
-                for L, out in zip(self.bot, bufs["bot_act"]):
-                    fwd16(L, h, out)
-                    h = out
-
-        def early_sort():  # the backward's sort on the side stream, beside the forward
-            s0 = torch.cuda.current_stream(self.dev)
-            idx, off = st["csr"] = self._phys_csr(batch, B)
-            self._side.wait_stream(s0)
-            with torch.cuda.stream(self._side), prof("tbe_sort"):
-                ops.tbe_backward_sort(self.weights, self.row_base, self.T_phys, B, idx, off,
-                                      self._ws_tbe(idx.numel()), batch.max_per_table,
-                                      error_flag=self.tbe_error_flag)
-            st["sorted"] = self._side
-
-        def fwd_single():
-            es = (self.early_sort and conc and self.T_local > 0 and presort
-                  and not 0 < batch.max_per_table <= ops.TBE_PRESORT_SEG_CAP)
-            if es and self.early_sort != 2:
-                early_sort()
-            lookup()
-            if es and self.early_sort == 2:
-                early_sort()
-            bottom_fwd()
-
-        def top():  # interaction, top MLP, head, top backward
-            x, feats = self._features(bufs, Bl)
-            with record_function("module::forward_pass::interaction"), prof("interaction_fwd"):
-                if gather:
-                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
-                                                cfg.arch_interaction_itself, out=bufs["R"],
-                                                error_flag=self.tbe_error_flag)
-                else:
-                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
-                                         cfg.arch_interaction_itself, out=bufs["R"])
-            h = bufs["R"]
-            with record_function("module::forward_pass::top_mlp"):
-                for L, out in zip(self.top[:-1], bufs["top_act"]):
-                    fwd16(L, h, out)
-                    h = out
-            last = self.top[-1]
-            G = bufs["g"]
-            gi = 0
-            g = G[gi][:, :last.Kp]
-            with record_function("## Loss Compute ##"), prof("head"):
-                ops.head_step(h[:, :last.Kp], last.W[0, :last.Kp], batch.target,
-                              cfg.loss_function, cfg.loss_threshold, 1.0, prob=bufs["prob"],
-                              dz=bufs["dz"], loss_out=bufs["loss"], dX=g,
-                              relu_mask=len(self.top) > 1,
-                              dw=None if fused_opt else last.gW[0, :last.Kp],
-                              lr=lr if fused_opt else 0.0,
-                              workspace=self._ws_head_step(Bl, last.Kp), defer=False)
-            with record_function("## Backward ##"):
-                for li in range(len(self.top) - 2, -1, -1):
-                    L = self.top[li]
-                    inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
-                    gn = (gi + 1) % 3
-                    dgrad16(L, g, inp if li > 0 else None, G[gn])
-                    wgrad16(L, g, inp)
-                    g, gi = G[gn], gn
-            st.update(x=x, feats=feats, g=g)
-
-        def interaction_bwd():
-            x, feats, g = st.pop("x"), st.pop("feats"), st.pop("g")
-            _, gfeats = self._features(bufs, Bl, grad=True)
-            with record_function("## Backward ##"), prof("interaction_bwd"):
-                if gather:
-                    ops.interact_backward_gather(x, self.weights, self.row_base, batch.indices,
-                                                 g[:, :self.num_int], cfg.arch_interaction_itself,
-                                                 grad_x=bufs["gx"], grad_ly=gfeats, relu_x=True)
-                else:
-                    ops.interact_backward(cfg.arch_interaction_op, x, feats, g[:, :self.num_int],
-                                          cfg.arch_interaction_itself, grad_x=bufs["gx"],
-                                          grad_ly=gfeats, relu_x=True)
-
-        def middle():
-            top()
-            interaction_bwd()
-
-        def bottom_bwd():
-            g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
-            for li in range(self.n_bot - 1, -1, -1):
-                L = self.bot[li]
-                inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
-                if li > 0:
-                    dgrad16(L, g, inp, bufs["gb"][li % 2])
-                wgrad16(L, g, inp)
-                if li > 0:
-                    g = bufs["gb"][li % 2]
-
-        def emb_bwd():
-            with prof("tbe_bwd"):
-                if self.T_local == 0:
-                    return
-                mode = "rowwise_adagrad" if cfg.optimizer == "rwsadagrad" else "sgd"
-                idx, off = st["csr"]
-                grad = bufs["dE"]
-                if self.qr_active:
-                    ops.qr_pool_combine_backward(cfg.qr_operation, self.T_local, B, self.D,
-                                                 self._qr_pq, self._qr_pr, bufs["P"],
-                                                 bufs["dE"], bufs["dP"])
-                    grad = bufs["dP"]
-                s1 = st.pop("sorted", None)
-                if s1 is not None:  # join the early sort
-                    torch.cuda.current_stream(self.dev).wait_stream(s1)
-                ops.tbe_backward(mode, self.weights, self.row_base, self.T_phys, B, idx, off,
-                                 grad, lr=elr, eps=cfg.adagrad_eps, momentum=self.momentum,
-                                 grad_batch_stride=grad.stride(0),
-                                 workspace=self._ws_tbe(idx.numel()),
-                                 max_lookups_per_table=batch.max_per_table,
-                                 error_flag=self.tbe_error_flag,
-                                 presorted=ops.PRESORTED_ANY if s1 is not None else presort)
-
-        @record_function("## Backward ##")
-        def backward_single():
-            bottom_bwd()
-            emb_bwd()
-
-        def dense_update():
-            with record_function("## Backward ##"), prof("dense_update"):
-                scale = 1.0 / self.world
-                if cfg.optimizer == "sgd":
-                    ops.sgd_update(self.params, self.grads, lr_w)
-                else:
-                    ops.adagrad_update(self.params, self.grads, self.adagrad_sum, lr,
-                                       cfg.adagrad_eps, grad_scale=scale)
-
-        def done():
-            self.step_count += 1
-
-        if not dist:
-            segs = [("gpu", self._with_tick(fwd_single)), ("gpu", middle),
-                    ("gpu", backward_single)]
-            if not fused_opt:
-                segs.append(("gpu", dense_update))
-            return segs + [("host", done)]
-        lookup = self._with_tick(lookup)
-
-        def ar(bucket):
-            def start():
-                g = self.grads[self.n_bot_params:] if bucket == "top" else \
-                    self.grads[:self.n_bot_params]
-                st["ar_" + bucket] = self.comm.allreduce(g)
-            return start
-
-        def wait(key):
-            return lambda: st.pop(key).wait()
-
-        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
-        a2a_bwd = lambda: st.__setitem__("a2a", self._alltoall_bwd(bufs, Bl))  # noqa: E731
-        bwd = lambda fn: record_function("## Backward ##")(fn)  # noqa: E731
-        # the role-free orders of segments(): each captured all-reduce is waited in the graph
-        # that issues it; on other comms the top bucket's all-reduce starts right after the
-        # top backward
-        if getattr(self.comm, "capture_ar", False):
-            return [
-                ("gpu", lookup), ("a2a", a2a_fwd), ("gpu", bottom_fwd), ("a2a", wait("a2a")),
-                ("gpu", top), ("gpu", interaction_bwd), ("a2a", a2a_bwd), ("ar", ar("top")),
-                ("gpu", bwd(bottom_bwd)), ("ar", wait("ar_top")), ("a2a", wait("a2a")),
-                ("ar", ar("bot")), ("gpu", bwd(emb_bwd)), ("ar", wait("ar_bot")),
-                ("gpu", dense_update), ("host", done),
-            ]
-        return [
-            ("gpu", lookup), ("a2a", a2a_fwd), ("gpu", bottom_fwd), ("a2a", wait("a2a")),
-            ("gpu", top), ("ar", ar("top")), ("gpu", interaction_bwd), ("a2a", a2a_bwd),
-            ("gpu", bwd(bottom_bwd)), ("ar", ar("bot")), ("a2a", wait("a2a")),
-            ("gpu", bwd(emb_bwd)), ("ar", wait("ar_top")), ("ar", wait("ar_bot")),
-            ("gpu", dense_update), ("host", done),
         ]
 
     def _ws_wgrad16(self, bufs, M: int, N: int, K: int) -> Optional[torch.Tensor]:
@@ -1534,10 +1408,6 @@ class DLRMTrainer:
                           self._qr_kind, self._qr_coll, mx if mx > 0 else n_log, pidx, poff,
                           error_flag=self.tbe_error_flag)
         return pidx, poff
-
-    def _qr_combine(self, bufs, B: int) -> None:
-        ops.qr_pool_combine_forward(self.cfg.qr_operation, self.T_local, B, self.D, self._qr_pq,
-                                    self._qr_pr, bufs["P"], bufs["E"])
 
     def capture(self, batch: Batch, pool=None, whole: Optional[bool] = None):
         """A replayable step for ``batch``.  whole (default: one GPU, or a comm whose
@@ -1644,11 +1514,11 @@ class DLRMTrainer:
 
     def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32"):
         """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
-        ``segments()``: the lookup (dlrm_tbe_forward; nothing of the backward's sort), the
-        bottom MLP (one GPU: beside the lookup on the side stream when the "fwd" overlap is
-        on; several: beside the all-to-all), the interaction (one GPU, one-hot batches: the
-        gather-fused one, then no lookup launch at all), the top MLP forwards and
-        dlrm_head_predict.
+        ``segments()`` and built from the same pieces (_build): the lookup
+        (dlrm_tbe_forward; nothing of the backward's sort), the bottom MLP (one GPU: beside
+        the lookup on the side stream when the "fwd" overlap is on; several: beside the
+        all-to-all), the interaction (one GPU, one-hot batches: the gather-fused one, then
+        no lookup launch at all), the top MLP forwards and dlrm_head_predict.
 
         ``precision`` "bf16" | "fp16" (the reference's --inference-only
         --quantize-mlp-with-bit 16, dlrm_s_pytorch.py:1757-1781): every bottom- and top-MLP
@@ -1658,108 +1528,7 @@ class DLRMTrainer:
         used.  The lookup, the interaction, the all-to-all and the head (its K -> 1 layer
         stays fp32) are the fp32 path's.  Only out[:, :N] of an activation buffer is
         written, so the constant-1 columns the training step relies on stay."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
-        p16 = precision != "fp32"
-        cfg = self.cfg
-        Bl = batch.X.shape[0]
-        B = Bl * self.world
-        n_off = self.T_local * B + 1
-        if self.T_local > 0 and batch.offsets.numel() != n_off:
-            raise ValueError(f"batch offsets hold {batch.offsets.numel()} entries, expected "
-                             f"T_local*B+1 = {n_off} (B = {Bl} x {self.world} ranks)")
-        bufs = self._buffers(Bl, B)
-        pb = self._predict_bufs(bufs)
-        dist = self.distributed
-        c_fwd = self.concurrent and "fwd" in self.overlaps and not dist
-        gather = not dist and self._gather_applies(batch)
-        st = {}
-
-        def gemm(problems, side=False):
-            key = "ws_side" if side else "ws"
-            need = ops.gemm_group_workspace_size(problems)
-            if need > pb[key].numel():  # first use of this batch size (not in capture)
-                pb[key] = torch.zeros(need, dtype=torch.uint8, device=self.dev)
-            ops.gemm_group(problems, pb[key], self.dev)
-
-        def lookup():
-            if self.T_local == 0 or gather:
-                return _EMPTY
-            with record_function("module::forward_pass::embedding_lookup"):
-                idx, off = self._phys_csr(batch, B)
-                out = bufs["P"] if self.qr_active else bufs["E"]
-                ops.tbe_forward(self.weights, self.row_base, self.T_phys, B, idx, off, out=out,
-                                out_batch_stride=out.stride(0), error_flag=self.tbe_error_flag)
-                if self.qr_active:
-                    self._qr_combine(bufs, B)
-
-        def linear16(L, h, out):
-            ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True, out=out[:, :L.N],
-                                 dtype=precision)
-
-        def bottom_fwd(side=False):
-            with record_function("module::forward_pass::bottom_mlp"):
-                if p16:
-                    h = batch.X
-                    for L, out in zip(self.bot, bufs["bot_act"]):
-                        linear16(L, h, out)
-                        h = out
-                    return
-                chain = self._bottom_chain(batch, bufs, sort_wgs=0, standalone=True)
-                if chain is not None:
-                    ops.mlp_chain_forward(chain, self.dev)
-                    return
-                h = batch.X
-                for L, out in zip(self.bot, bufs["bot_act"]):
-                    gemm([self._fwd(L, h, out)], side=side)
-                    h = out
-
-        def fwd_single():
-            s0 = torch.cuda.current_stream(self.dev)
-            if not c_fwd:
-                lookup()
-                bottom_fwd()
-                return
-            self._side.wait_stream(s0)
-            lookup()
-            with torch.cuda.stream(self._side):
-                bottom_fwd(side=True)
-            s0.wait_stream(self._side)
-
-        def top_fwd():
-            x, feats = self._features(bufs, Bl)
-            with record_function("module::forward_pass::interaction"):
-                if gather:
-                    ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
-                                                cfg.arch_interaction_itself, out=bufs["R"],
-                                                error_flag=self.tbe_error_flag)
-                else:
-                    ops.interact_forward(cfg.arch_interaction_op, x, feats,
-                                         cfg.arch_interaction_itself, out=bufs["R"])
-            h = bufs["R"]
-            with record_function("module::forward_pass::top_mlp"):
-                for L, out in zip(self.top[:-1], bufs["top_act"]):
-                    if p16:
-                        linear16(L, h, out)
-                    else:
-                        gemm([self._fwd(L, h, out)])
-                    h = out
-                last = self.top[-1]
-                ops.head_predict(h[:, :last.Kp], last.W[0, :last.Kp], cfg.loss_threshold,
-                                 prob=pb["prob"],
-                                 target=batch.target if metrics is not None else None,
-                                 state=metrics)
-
-        if not dist:
-            return [("gpu", fwd_single), ("gpu", top_fwd)]
-        a2a_fwd = lambda: st.__setitem__("a2a", self._alltoall_fwd(bufs, Bl))  # noqa: E731
-        return [
-            ("gpu", lookup),
-            ("a2a", a2a_fwd),
-            ("gpu", bottom_fwd),
-            ("a2a", lambda: st.pop("a2a").wait()),
-            ("gpu", top_fwd),
-        ]
+        return self._build(batch, predict=(metrics, _precision(precision)))
 
     def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32"):
         """A replayable forward-only pass for ``batch`` (capture()'s modes over
@@ -1767,8 +1536,7 @@ class DLRMTrainer:
         Each call of the returned callable scores the batch's current contents into the
         tensor predict() returns; with ``metrics`` every call appends B_local samples (the
         log's cursor lives on the device).  ``precision``: as predict_segments."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+        _precision(precision)
         run, _mode, _graphs = self._capture_segments(
             lambda: self.predict_segments(batch, metrics, precision), pool, None)
         return run
@@ -1779,8 +1547,7 @@ class DLRMTrainer:
         per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
         batches are copied into.  Index errors are checked once, at the end.
         ``precision``: as predict_segments (part of the graph key)."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+        _precision(precision)
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
@@ -1857,33 +1624,6 @@ class DLRMTrainer:
         pr = self._wgrad(L, g, inp, fused_opt, lr, partial=parts[key], splits=s)
         return pr, ops.reduce_problem(pr)
 
-    def _gemm(self, problems, side=False):
-        """One grouped launch; it also carries the next pending pass of a deferred
-        embedding update (self._roles, set by the single-GPU backward)."""
-        with self._prof("gemm"):
-            ws = self._cur["gemm_ws_side" if side else "gemm_ws"]
-            need = ops.gemm_group_workspace_size(problems) if problems else 0
-            if need > ws.numel():  # first use of a new group shape: grow (not in capture)
-                ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
-                self._cur["gemm_ws_side" if side else "gemm_ws"] = ws
-            nxt = self._roles.pop(0) if self._roles and not side else None
-            role, phase = nxt if nxt is not None else (None, 0)
-            ops.gemm_group(problems, ws, self.dev, role=role, phase=phase)
-
-    def _colsum(self, *args, **kw):
-        with self._prof("colsum"):
-            ops.colsum(*args, **kw)
-
-    def _bias_and_w_head(self, last: _Layer, hin, dz, fused_opt, lr):
-        """Head layer (K -> 1): [dw | db] = sum_m dz[m] [hin[m] | 1] as one column sum."""
-        Bl = hin.shape[0]
-        if fused_opt:
-            self._colsum(hin[:, :last.Kp], scale=dz, sgd_param=last.W[0], lr=lr,
-                         workspace=self._ws_colsum(Bl, last.Kp))
-        else:
-            self._colsum(hin[:, :last.Kp], scale=dz, out=last.gW[0],
-                         workspace=self._ws_colsum(Bl, last.Kp))
-
     def _bottom_chain(self, batch: Batch, bufs, sort_wgs: Optional[int] = None,
                       standalone: bool = False):
         """The bottom MLP forward as a dlrm_mlp_chain (None when unsupported or disabled or,
@@ -1921,23 +1661,11 @@ class DLRMTrainer:
             self._tbe_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return self._tbe_ws
 
-    def _ws_colsum(self, M: int, N: int) -> torch.Tensor:
-        need = int(ops._lib.query("dlrm_colsum_workspace_size", M, max(N, 1024)))
-        if self._colsum_ws is None or self._colsum_ws.numel() < need:
-            self._colsum_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        return self._colsum_ws
-
     def _ws_head_step(self, M: int, K: int) -> torch.Tensor:
         need = int(ops._lib.query("dlrm_head_step_workspace_size", M, K))
-        if getattr(self, "_head_step_ws", None) is None or self._head_step_ws.numel() < need:
+        if self._head_step_ws is None or self._head_step_ws.numel() < need:
             self._head_step_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return self._head_step_ws
-
-    def _ws_head(self, M: int) -> torch.Tensor:
-        need = int(ops._lib.query("dlrm_head_workspace_size", M))
-        if self._head_ws is None or self._head_ws.numel() < need:
-            self._head_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        return self._head_ws
 
     # ------------------------------------------------------ communication --
     def _split_sizes(self, Bl: int):
