@@ -36,8 +36,10 @@ struct GradArgs {
 // The one-hot lookup fused into the interaction (dlrm_interact_dot_forward_gather): feature
 // f >= 1 of sample b is row row_base[f-1] + idx[(f-1) * B + b] of W (L = 1, table-major
 // CSR indices: the lookup of apply_emb with one index per bag); feature 0 stays fa.ptr[0].
+// The kernels' GATHER template argument: 0 = pooled features, 1 = fp32 rows gathered,
+// 2 = fp16 rows gathered (dlrm_interact_dot_forward_gather_f16, gather_load4_f16 below).
 struct GatherArgs {
-  const float* W;
+  const float* W;           // the row buffer; [rows][D] fp16 behind the pointer when GATHER == 2
   const int64_t* row_base;  // [F] device: table starts, row_base[F-1] = total rows
   const int32_t* idx;       // [(F-1) * B]
   int32_t* err;             // DLRM_TBE_ERR_INDEX on an index outside its table (may be null)
@@ -228,6 +230,30 @@ __device__ __forceinline__ int64_t gather_row(const GatherArgs& gt, int F, int B
   return -1;
 }
 
+// fp16 tables (GATHER == 2): a lane keeps its four columns [col, col + 4) of row f; it reads
+// them as one 8-byte load of four halves where the fp32 kernel reads a float4, and widens
+// them in registers (exact), so the LDS image and everything after it are the fp32 kernel's.
+// Feature 0 (x) stays fp32: only a lane of the first row group (`first`) can hold f == 0,
+// and there x's float4 is loaded by every lane and selected, so no load sits in a branch.
+// Lanes without a table row (f >= F, a bad index) read 8 valid bytes of x; callers zero them.
+template <int D>
+__device__ __forceinline__ float4 gather_load4_f16(const GatherArgs& gt, const float* xrow, int f,
+                                                   int64_t g, int col, bool first) {
+  const bool tab = f >= 1 && g >= 0;
+  const unsigned short* src = tab ? reinterpret_cast<const unsigned short*>(gt.W) + g * D + col
+                                  : reinterpret_cast<const unsigned short*>(xrow) + col;
+  const uint2 u = *reinterpret_cast<const uint2*>(src);
+  float4 v = make_float4((float)__builtin_bit_cast(_Float16, (unsigned short)(u.x & 0xffff)),
+                         (float)__builtin_bit_cast(_Float16, (unsigned short)(u.x >> 16)),
+                         (float)__builtin_bit_cast(_Float16, (unsigned short)(u.y & 0xffff)),
+                         (float)__builtin_bit_cast(_Float16, (unsigned short)(u.y >> 16)));
+  if (first) {
+    const float4 xv = *reinterpret_cast<const float4*>(xrow + col);
+    if (f == 0) v = xv;
+  }
+  return v;
+}
+
 template <int D>
 __device__ __forceinline__ float* grad_row_ptr(const GradArgs& ga, int F, int64_t b, int i0,
                                                int sub) {
@@ -247,7 +273,7 @@ __device__ __forceinline__ float* grad_row_ptr(const GradArgs& ga, int F, int64_
 // Forward: T (F x D) -> LDS with coalesced float4 loads; lane (f, h) then feeds T[f][k] for
 // its k-half as both MFMA operands (Z = T T^T, two accumulator chains); the strict lower
 // triangle and x are staged in LDS in output order and written as whole float4 rows.
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __global__ __launch_bounds__(256) void interact_dot_fwd_v4(int B, int F, FeatArgs fa, int self,
                                                            float* __restrict__ out,
                                                            int64_t ld_out, int width,
@@ -279,7 +305,12 @@ __global__ __launch_bounds__(256) void interact_dot_fwd_v4(int B, int F, FeatArg
       float4 v[NI];
 #pragma unroll
       for (int q = 0; q < NI; ++q) {
-        if constexpr (GATHER) {
+        if constexpr (GATHER == 2) {
+          const int f = q * RPI + sub;
+          const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
+          v[q] = gather_load4_f16<D>(gt, fa.ptr[0] + bl * fa.bs[0], f, g, 4 * c, q == 0);
+          if (f >= 1 && g < 0) v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (GATHER) {
           const int f = q * RPI + sub;
           const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
           const float* src = (f >= 1 && g >= 0) ? gt.W + g * D : fa.ptr[0] + bl * fa.bs[0];
@@ -340,7 +371,7 @@ __global__ __launch_bounds__(256) void interact_dot_fwd_v4(int B, int F, FeatArg
 // T columns it consumed, then every feature's gradient row leaves as whole float4 rows.
 // Feature 0 (the bottom-MLP output x) gets dR[0:D] added and, with relu_x, the ReLU' mask
 // of x applied (the backward of the bottom MLP's last ReLU, fused).
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __global__ __launch_bounds__(256) void interact_dot_bwd_v3(int B, int F, FeatArgs fa, int self,
                                                            const float* __restrict__ gout,
                                                            int64_t ld_g, GradArgs ga,
@@ -373,7 +404,12 @@ __global__ __launch_bounds__(256) void interact_dot_bwd_v3(int B, int F, FeatArg
       float4 v[NI];
 #pragma unroll
       for (int q = 0; q < NI; ++q) {
-        if constexpr (GATHER) {
+        if constexpr (GATHER == 2) {
+          const int f = q * RPI + sub;
+          const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
+          v[q] = gather_load4_f16<D>(gt, fa.ptr[0] + bl * fa.bs[0], f, g, 4 * c, q == 0);
+          if (f >= 1 && g < 0) v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (GATHER) {
           const int f = q * RPI + sub;
           const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
           const float* src = (f >= 1 && g >= 0) ? gt.W + g * D : fa.ptr[0] + bl * fa.bs[0];
@@ -515,7 +551,7 @@ __device__ __forceinline__ const float* row_ptr_n(const FeatArgs& fa, int F, int
   return p + b * bs;
 }
 
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __global__ __launch_bounds__(256) void interact_dot_bwd_v4(int B, int F, FeatArgs fa, int self,
                                                            const float* __restrict__ gout,
                                                            int64_t ld_g, GradArgs ga,
@@ -551,7 +587,12 @@ __global__ __launch_bounds__(256) void interact_dot_bwd_v4(int B, int F, FeatArg
       float4 v[NI];
 #pragma unroll
       for (int q = 0; q < NI; ++q) {
-        if constexpr (GATHER) {
+        if constexpr (GATHER == 2) {
+          const int f = q * RPI + sub;
+          const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
+          v[q] = gather_load4_f16<D>(gt, fa.ptr[0] + b * fa.bs[0], f, g, c0 + 4 * c, q == 0);
+          if (f >= 1 && g < 0) v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (GATHER) {
           const int f = q * RPI + sub;
           const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
           const float* src = (f >= 1 && g >= 0) ? gt.W + g * D : fa.ptr[0] + b * fa.bs[0];
@@ -676,7 +717,7 @@ __device__ __forceinline__ float* grad_ptr_w(const GradArgs& ga, int F, int64_t 
 }
 
 // T (F <= 32 rows, rows >= F zero) of sample b -> Tl (pitch DP), the whole workgroup.
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __device__ __forceinline__ void v5_load_t(int B, int F, const FeatArgs& fa, const GatherArgs& gt,
                                           int64_t b, float* Tl, bool flag) {
   constexpr int NT = 2 * D, C4 = D / 4, RPW = 64 / C4, RPB = NT / C4, NI = 32 / RPB;
@@ -690,17 +731,22 @@ __device__ __forceinline__ void v5_load_t(int B, int F, const FeatArgs& fa, cons
     if constexpr (GATHER) {
       const float* src = fa.ptr[0] + b * fa.bs[0];
       bool zero = false;
+      int64_t g = -1;  // the global row (fp16 tables address it in halves)
       if (f >= 1 && f < F) {
         const int64_t lo = gt.row_base[f - 1], n = gt.row_base[f] - lo;
         const int64_t r = gt.idx[(int64_t)(f - 1) * B + b];
         if (r >= 0 && r < n) {
-          src = gt.W + (lo + r) * D;
+          g = lo + r;
+          if constexpr (GATHER != 2) src = gt.W + g * D;
         } else {
           zero = true;
           if (flag && c == 0 && gt.err) atomicOr(gt.err, DLRM_TBE_ERR_INDEX);
         }
       }
-      v[q] = *reinterpret_cast<const float4*>(src + 4 * c);
+      if constexpr (GATHER == 2)
+        v[q] = gather_load4_f16<D>(gt, src, f, g, 4 * c, q == 0);
+      else
+        v[q] = *reinterpret_cast<const float4*>(src + 4 * c);
       if (zero) v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
       v[q] = *reinterpret_cast<const float4*>(row_ptr_w<D>(fa, F, b, i0, sw) + 4 * c);
@@ -714,7 +760,7 @@ __device__ __forceinline__ void v5_load_t(int B, int F, const FeatArgs& fa, cons
   }
 }
 
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __global__ __launch_bounds__(2 * D) void interact_dot_fwd_v5(int B, int F, FeatArgs fa, int self,
                                                              float* __restrict__ out,
                                                              int64_t ld_out, int width,
@@ -763,7 +809,7 @@ __global__ __launch_bounds__(2 * D) void interact_dot_fwd_v5(int B, int F, FeatA
   }
 }
 
-template <int D, bool GATHER>
+template <int D, int GATHER>
 __global__ __launch_bounds__(2 * D) void interact_dot_bwd_v5(int B, int F, FeatArgs fa, int self,
                                                              const float* __restrict__ gout,
                                                              int64_t ld_g, GradArgs ga,
@@ -1138,21 +1184,22 @@ extern "C" int dlrm_interact_cat_backward(int32_t B, int32_t F, int32_t D,
 // One-hot lookup fused into the interaction (one GPU, L = 1): features 1..F-1 are gathered
 // straight from the table buffer (no [B, T, D] pooled-embedding round trip through HBM).
 // Same math and output as dlrm_interact_dot_forward on the looked-up rows.
-extern "C" int dlrm_interact_dot_forward_gather(int32_t B, int32_t F, int32_t D, const float* x,
-                                                int64_t x_bstride, const float* weights,
-                                                const int64_t* row_base, const int32_t* indices,
-                                                int32_t self_interaction, float* out,
-                                                int64_t ld_out, int32_t* error_flag,
-                                                dlrm_stream_t stream) {
-  const char* name = "dlrm_interact_dot_forward_gather";
+// G = 1: fp32 rows; G = 2: fp16 rows (one 8-byte read per lane, widened in registers).
+namespace {
+template <int G>
+int forward_gather(const char* name, int32_t B, int32_t F, int32_t D, const float* x,
+                   int64_t x_bstride, const float* weights, const int64_t* row_base,
+                   const int32_t* indices, int32_t self_interaction, float* out, int64_t ld_out,
+                   int32_t* error_flag, dlrm_stream_t stream) {
   DLRM_ARG(B >= 0 && F >= 2 && F <= 32, "%s: need F in [2,32]", name);
   DLRM_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, DLRM_ERR_UNSUPPORTED,
                "%s: D must be 16, 32, 64 or 128", name);
   if (B == 0) return DLRM_OK;
   DLRM_ARG(x && weights && row_base && indices && out, "%s: null pointer", name);
-  DLRM_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0 &&
-               x_bstride % 4 == 0,
-           "%s: x / weights must be 16-B aligned, x_bstride %% 4 == 0", name);
+  DLRM_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+               (reinterpret_cast<uintptr_t>(weights) & (G == 2 ? 7 : 15)) == 0 && x_bstride % 4 == 0,
+           "%s: x must be 16-B aligned, weights %d-B aligned, x_bstride %% 4 == 0", name,
+           G == 2 ? 8 : 16);
   const int npairs = self_interaction ? F * (F + 1) / 2 : F * (F - 1) / 2;
   DLRM_ARG(ld_out >= D + npairs, "%s: ld_out < D + pairs", name);
   FeatArgs fa{};
@@ -1162,10 +1209,10 @@ extern "C" int dlrm_interact_dot_forward_gather(int32_t B, int32_t F, int32_t D,
   hipStream_t st = dlrm::as_stream(stream);
   if (fwd_version(D, B) == 5) {
     if (D == 64)
-      hipLaunchKernelGGL((interact_dot_fwd_v5<64, true>), dim3(v5_grid(B)), dim3(128), 0, st, B, F,
+      hipLaunchKernelGGL((interact_dot_fwd_v5<64, G>), dim3(v5_grid(B)), dim3(128), 0, st, B, F,
                          fa, self_interaction ? 1 : 0, out, ld_out, width, gt);
     else
-      hipLaunchKernelGGL((interact_dot_fwd_v5<128, true>), dim3(v5_grid(B)), dim3(256), 0, st, B,
+      hipLaunchKernelGGL((interact_dot_fwd_v5<128, G>), dim3(v5_grid(B)), dim3(256), 0, st, B,
                          F, fa, self_interaction ? 1 : 0, out, ld_out, width, gt);
     DLRM_LAUNCH_CHECK(name);
     return DLRM_OK;
@@ -1174,31 +1221,57 @@ extern "C" int dlrm_interact_dot_forward_gather(int32_t B, int32_t F, int32_t D,
   const size_t lds = 4 * (32 * (size_t)(D + 4) + D + 32 * 33 / 2 + 4) * sizeof(float);
   const int grid = (int)std::min<int64_t>(dlrm::ceil_div(B, 4), 8192);
 #define L4G(DD)                                                                              \
-  hipLaunchKernelGGL((interact_dot_fwd_v4<DD, true>), dim3(grid), dim3(256), lds, st, B, F, fa, \
+  hipLaunchKernelGGL((interact_dot_fwd_v4<DD, G>), dim3(grid), dim3(256), lds, st, B, F, fa, \
                      self_interaction ? 1 : 0, out, ld_out, width, vec_out, gt)
   if (D == 16) L4G(16); else if (D == 32) L4G(32); else if (D == 64) L4G(64); else L4G(128);
 #undef L4G
   DLRM_LAUNCH_CHECK(name);
   return DLRM_OK;
 }
+}  // namespace
+
+extern "C" int dlrm_interact_dot_forward_gather(int32_t B, int32_t F, int32_t D, const float* x,
+                                                int64_t x_bstride, const float* weights,
+                                                const int64_t* row_base, const int32_t* indices,
+                                                int32_t self_interaction, float* out,
+                                                int64_t ld_out, int32_t* error_flag,
+                                                dlrm_stream_t stream) {
+  return forward_gather<1>("dlrm_interact_dot_forward_gather", B, F, D, x, x_bstride, weights,
+                           row_base, indices, self_interaction, out, ld_out, error_flag, stream);
+}
+
+// The same on [rows][D] fp16 tables (ABI v15): x, the output and the arithmetic stay fp32.
+extern "C" int dlrm_interact_dot_forward_gather_f16(int32_t B, int32_t F, int32_t D,
+                                                    const float* x, int64_t x_bstride,
+                                                    const void* weights, const int64_t* row_base,
+                                                    const int32_t* indices,
+                                                    int32_t self_interaction, float* out,
+                                                    int64_t ld_out, int32_t* error_flag,
+                                                    dlrm_stream_t stream) {
+  return forward_gather<2>("dlrm_interact_dot_forward_gather_f16", B, F, D, x, x_bstride,
+                           static_cast<const float*>(weights), row_base, indices,
+                           self_interaction, out, ld_out, error_flag, stream);
+}
 
 // Its backward: T re-gathered from the same (not yet updated) rows; gradients as
 // dlrm_interact_dot_backward (grad_ptrs[f] / grad_bstrides[f], e.g. the [B, T, D] buffer
 // the TBE backward reads), ReLU' of x optional.
-extern "C" int dlrm_interact_dot_backward_gather(
-    int32_t B, int32_t F, int32_t D, const float* x, int64_t x_bstride, const float* weights,
-    const int64_t* row_base, const int32_t* indices, int32_t self_interaction,
-    const float* grad_out, int64_t ld_gout, float* const* grad_ptrs,
-    const int64_t* grad_bstrides, int32_t relu_x, dlrm_stream_t stream) {
-  const char* name = "dlrm_interact_dot_backward_gather";
+namespace {
+template <int G>
+int backward_gather(const char* name, int32_t B, int32_t F, int32_t D, const float* x,
+                    int64_t x_bstride, const float* weights, const int64_t* row_base,
+                    const int32_t* indices, int32_t self_interaction, const float* grad_out,
+                    int64_t ld_gout, float* const* grad_ptrs, const int64_t* grad_bstrides,
+                    int32_t relu_x, dlrm_stream_t stream) {
   DLRM_ARG(B >= 0 && F >= 2 && F <= 32, "%s: need F in [2,32]", name);
   DLRM_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, DLRM_ERR_UNSUPPORTED,
                "%s: D must be 16, 32, 64 or 128", name);
   if (B == 0) return DLRM_OK;
   DLRM_ARG(x && weights && row_base && indices && grad_out, "%s: null pointer", name);
-  DLRM_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0 &&
-               x_bstride % 4 == 0,
-           "%s: x / weights must be 16-B aligned, x_bstride %% 4 == 0", name);
+  DLRM_ARG((reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+               (reinterpret_cast<uintptr_t>(weights) & (G == 2 ? 7 : 15)) == 0 && x_bstride % 4 == 0,
+           "%s: x must be 16-B aligned, weights %d-B aligned, x_bstride %% 4 == 0", name,
+           G == 2 ? 8 : 16);
   const int npairs = self_interaction ? F * (F + 1) / 2 : F * (F - 1) / 2;
   DLRM_ARG(ld_gout >= D + npairs, "%s: ld_gout < D + pairs", name);
   GradArgs ga{};
@@ -1215,11 +1288,11 @@ extern "C" int dlrm_interact_dot_backward_gather(
   const int ver = bwd_version(D, B);
   if (ver == 5) {
     if (D == 64)
-      hipLaunchKernelGGL((interact_dot_bwd_v5<64, true>), dim3(v5_grid(B)), dim3(128), 0, st, B, F,
+      hipLaunchKernelGGL((interact_dot_bwd_v5<64, G>), dim3(v5_grid(B)), dim3(128), 0, st, B, F,
                          fa, self_interaction ? 1 : 0, grad_out, ld_gout, ga, relu_x ? 1 : 0, vec_g,
                          gt);
     else
-      hipLaunchKernelGGL((interact_dot_bwd_v5<128, true>), dim3(v5_grid(B)), dim3(256), 0, st, B, F,
+      hipLaunchKernelGGL((interact_dot_bwd_v5<128, G>), dim3(v5_grid(B)), dim3(256), 0, st, B, F,
                          fa, self_interaction ? 1 : 0, grad_out, ld_gout, ga, relu_x ? 1 : 0, vec_g,
                          gt);
     DLRM_LAUNCH_CHECK(name);
@@ -1230,7 +1303,7 @@ extern "C" int dlrm_interact_dot_backward_gather(
     const size_t lds4 = 4 * (32 * (size_t)(cb + 4) + D + 32 * 33 / 2 + 4) * sizeof(float);
     const int grid4 = (int)std::min<int64_t>(dlrm::ceil_div((int64_t)B * nblk, 4), 8192);
 #define L4G(DD)                                                                               \
-  hipLaunchKernelGGL((interact_dot_bwd_v4<DD, true>), dim3(grid4), dim3(256), lds4, st, B, F, fa, \
+  hipLaunchKernelGGL((interact_dot_bwd_v4<DD, G>), dim3(grid4), dim3(256), lds4, st, B, F, fa, \
                      self_interaction ? 1 : 0, grad_out, ld_gout, ga, relu_x ? 1 : 0, vec_g, gt)
     if (D == 16) L4G(16); else if (D == 32) L4G(32); else if (D == 64) L4G(64); else L4G(128);
 #undef L4G
@@ -1240,10 +1313,32 @@ extern "C" int dlrm_interact_dot_backward_gather(
   const size_t lds = 4 * (32 * (size_t)(D + 4) + D + 32 * 33 / 2 + 4) * sizeof(float);
   const int grid = (int)std::min<int64_t>(dlrm::ceil_div(B, 4), 8192);
 #define L3G(DD)                                                                               \
-  hipLaunchKernelGGL((interact_dot_bwd_v3<DD, true>), dim3(grid), dim3(256), lds, st, B, F, fa,  \
+  hipLaunchKernelGGL((interact_dot_bwd_v3<DD, G>), dim3(grid), dim3(256), lds, st, B, F, fa,  \
                      self_interaction ? 1 : 0, grad_out, ld_gout, ga, relu_x ? 1 : 0, vec_g, gt)
   if (D == 16) L3G(16); else if (D == 32) L3G(32); else if (D == 64) L3G(64); else L3G(128);
 #undef L3G
   DLRM_LAUNCH_CHECK(name);
   return DLRM_OK;
+}
+}  // namespace
+
+extern "C" int dlrm_interact_dot_backward_gather(
+    int32_t B, int32_t F, int32_t D, const float* x, int64_t x_bstride, const float* weights,
+    const int64_t* row_base, const int32_t* indices, int32_t self_interaction,
+    const float* grad_out, int64_t ld_gout, float* const* grad_ptrs,
+    const int64_t* grad_bstrides, int32_t relu_x, dlrm_stream_t stream) {
+  return backward_gather<1>("dlrm_interact_dot_backward_gather", B, F, D, x, x_bstride, weights,
+                            row_base, indices, self_interaction, grad_out, ld_gout, grad_ptrs,
+                            grad_bstrides, relu_x, stream);
+}
+
+extern "C" int dlrm_interact_dot_backward_gather_f16(
+    int32_t B, int32_t F, int32_t D, const float* x, int64_t x_bstride, const void* weights,
+    const int64_t* row_base, const int32_t* indices, int32_t self_interaction,
+    const float* grad_out, int64_t ld_gout, float* const* grad_ptrs,
+    const int64_t* grad_bstrides, int32_t relu_x, dlrm_stream_t stream) {
+  return backward_gather<2>("dlrm_interact_dot_backward_gather_f16", B, F, D, x, x_bstride,
+                            static_cast<const float*>(weights), row_base, indices,
+                            self_interaction, grad_out, ld_gout, grad_ptrs, grad_bstrides, relu_x,
+                            stream);
 }

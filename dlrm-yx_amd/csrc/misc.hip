@@ -265,13 +265,16 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// Element j of the call is element first + j of the seed's stream (first = 0: the whole
+// stream from its start; a caller that fills in chunks passes each chunk's offset).
 __global__ __launch_bounds__(256) void uniform_fill_kernel(float* __restrict__ out, int64_t n,
-                                                           float lo, float hi, uint64_t seed) {
+                                                           float lo, float hi, uint64_t seed,
+                                                           uint64_t first) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const uint64_t key = splitmix64(seed);
   for (int64_t j = i; j < n; j += stride) {
-    const uint64_t x = splitmix64(key ^ (uint64_t)j);
+    const uint64_t x = splitmix64(key ^ (first + (uint64_t)j));
     const float u = (float)(x >> 40) * (1.f / 16777216.f);
     out[j] = lo + (hi - lo) * u;
   }
@@ -473,8 +476,19 @@ extern "C" int dlrm_uniform_fill(float* out, int64_t n, float lo, float hi, uint
   if (n == 0) return DLRM_OK;
   DLRM_ARG(out, "dlrm_uniform_fill: null pointer");
   hipLaunchKernelGGL(uniform_fill_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
-                     dlrm::as_stream(stream), out, n, lo, hi, seed);
+                     dlrm::as_stream(stream), out, n, lo, hi, seed, (uint64_t)0);
   DLRM_LAUNCH_CHECK("dlrm_uniform_fill");
+  return DLRM_OK;
+}
+
+extern "C" int dlrm_uniform_fill_at(float* out, int64_t n, float lo, float hi, uint64_t seed,
+                                    int64_t first, dlrm_stream_t stream) {
+  DLRM_ARG(n >= 0 && first >= 0, "dlrm_uniform_fill_at: bad n / first");
+  if (n == 0) return DLRM_OK;
+  DLRM_ARG(out, "dlrm_uniform_fill_at: null pointer");
+  hipLaunchKernelGGL(uniform_fill_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0,
+                     dlrm::as_stream(stream), out, n, lo, hi, seed, (uint64_t)first);
+  DLRM_LAUNCH_CHECK("dlrm_uniform_fill_at");
   return DLRM_OK;
 }
 

@@ -1171,6 +1171,24 @@ extern "C" int dlrm_tbe_backward_sgd_f16(void* weights, int64_t D, const int64_t
                       "dlrm_tbe_backward_sgd_f16");
 }
 
+extern "C" int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int64_t* row_base,
+                                             int32_t T, int32_t B, const void* indices,
+                                             int32_t index_bits, const void* offsets,
+                                             int32_t offset_bits, int64_t num_lookups,
+                                             int64_t total_rows, const float* per_sample_weights,
+                                             const float* grad_out, int64_t grad_batch_stride,
+                                             const float* lr_dev, int64_t max_lookups_per_table,
+                                             void* workspace, size_t workspace_bytes,
+                                             int32_t* error_flag, int32_t presorted,
+                                             dlrm_stream_t stream) {
+  DLRM_ARG(lr_dev, "dlrm_tbe_backward_sgd_f16_dev: null lr_dev");
+  return bwd_dispatch(MODE_SGD_F16, static_cast<float*>(weights), nullptr, D, row_base, T, B,
+                      indices, index_bits, offsets, offset_bits, num_lookups, total_rows,
+                      per_sample_weights, grad_out, grad_batch_stride, 0.f, 0.f, workspace,
+                      workspace_bytes, max_lookups_per_table, error_flag, presorted, nullptr, stream,
+                      "dlrm_tbe_backward_sgd_f16_dev", false, lr_dev);
+}
+
 extern "C" int dlrm_tbe_backward_rowwise_adagrad(
     float* weights, float* momentum, int64_t D, const int64_t* row_base, int32_t T, int32_t B,
     const void* indices, int32_t index_bits, const void* offsets, int32_t offset_bits,

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 14
+ABI_VERSION = 15
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -196,6 +196,17 @@ SIGNATURES = {
                                               c_int32, P, P]),
     "dlrm_linear16_wgrad_dev": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int64, P,
                                           c_int64, c_int32, P, P, c_int64, P, c_size_t, P]),
+    # ABI v15: fp16 embedding tables in the fused engine (gather-fused interaction on fp16
+    # rows; the fp16 exact-SGD update at a device-resident rate)
+    "dlrm_interact_dot_forward_gather_f16": (c_int32, [c_int32, c_int32, c_int32, P, c_int64, P,
+                                                       P, P, c_int32, P, c_int64, P, P]),
+    "dlrm_interact_dot_backward_gather_f16": (c_int32, [c_int32, c_int32, c_int32, P, c_int64, P,
+                                                        P, P, c_int32, P, c_int64, P, P, c_int32,
+                                                        P]),
+    "dlrm_tbe_backward_sgd_f16_dev": (c_int32, [P, c_int64, P, c_int32, c_int32, P, c_int32, P,
+                                                c_int32, c_int64, c_int64, P, P, c_int64, P,
+                                                c_int64, P, c_size_t, P, c_int32, P]),
+    "dlrm_uniform_fill_at": (c_int32, [P, c_int64, c_float, c_float, c_uint64, c_int64, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

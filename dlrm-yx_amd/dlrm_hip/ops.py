@@ -362,14 +362,15 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
                  workspace: Optional[torch.Tensor] = None,
                  max_lookups_per_table: int = 0,
                  error_flag: Optional[torch.Tensor] = None, presorted: int = False) -> None:
-    """mode: 'sgd' (fused exact SGD; fp32 or fp16 weights), 'rowwise_adagrad' (fused
+    """mode: 'sgd' (fused exact SGD; fp32 or fp16 weights; 'sgd_f16' names the fp16 case and
+    refuses fp32 weights), 'rowwise_adagrad' (fused
     RWSAdagrad) or 'dense' (weights is a gradient buffer to accumulate into).  max_lookups_per_table:
     upper bound on any table's lookups (0 = unknown); <= 4096 selects the per-table LDS
     sort (bitwise the same result as the device-wide radix sort).  ``error_flag``: device
     int32 that receives TBE_ERR_INDEX / TBE_ERR_TABLE_CAP bits (see check_tbe_errors).
     ``presorted``: True - the per-table sort ran in tbe_forward_presort; PRESORTED_ANY -
-    tbe_backward_sort ran for this batch.  ``lr``: a float, or (fp32 'sgd' and
-    'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run."""
+    tbe_backward_sort ran for this batch.  ``lr``: a float, or ('sgd', fp32 or fp16
+    weights, and 'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     lr_dev = _lr_dev(lr, "tbe_backward: lr")
     D = weights.shape[1]
@@ -385,11 +386,15 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
                    grad_batch_stride)
     st = _stream(weights.device)
     mx = int(max_lookups_per_table)
-    if mode == "sgd" and weights.dtype == torch.float16:
+    if mode == "sgd_f16" and weights.dtype != torch.float16:
+        raise ValueError("tbe_backward: mode 'sgd_f16' takes fp16 weights")
+    if mode in ("sgd", "sgd_f16") and weights.dtype == torch.float16:
         if lr_dev is not None:
-            raise ValueError("tbe_backward: fp16 tables take a host float lr")
-        _lib.call("dlrm_tbe_backward_sgd_f16", _p(weights), *args_common, lr, mx,
-                  _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
+            _lib.call("dlrm_tbe_backward_sgd_f16_dev", _p(weights), *args_common, lr_dev, mx,
+                      _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
+        else:
+            _lib.call("dlrm_tbe_backward_sgd_f16", _p(weights), *args_common, lr, mx,
+                      _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
     elif mode == "sgd" and lr_dev is not None:
         _lib.call("dlrm_tbe_backward_sgd_dev", _p(weights), *args_common, lr_dev, mx,
                   _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
@@ -606,14 +611,26 @@ def interact_backward(op: str, x: torch.Tensor, ly, grad_out: torch.Tensor,
     return grad_x, grad_ly
 
 
+def _gather_entry(name: str, x: torch.Tensor, weights: torch.Tensor) -> str:
+    """The gather entry point for the table's row type ([rows, D] fp32 or fp16)."""
+    if weights.dtype == torch.float32:
+        return name
+    if weights.dtype == torch.float16:
+        return name + "_f16"
+    raise ValueError(f"gather interaction: fp32 or fp16 tables, not {weights.dtype}")
+
+
 def interact_forward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: torch.Tensor,
                             indices: torch.Tensor, self_interaction: bool = False,
                             out: Optional[torch.Tensor] = None,
                             error_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dot interaction of x and the one-hot lookups (L = 1) of T = len(row_base) - 1 tables
     gathered straight from ``weights`` (dlrm_interact_dot_forward_gather): the same R as
-    interact_forward(x, tbe_forward(...)) without the pooled [B, T, D] buffer."""
+    interact_forward(x, tbe_forward(...)) without the pooled [B, T, D] buffer.  fp16
+    ``weights`` take dlrm_interact_dot_forward_gather_f16: the rows are widened to fp32 as
+    they are loaded, x, R and the arithmetic stay fp32."""
     _check_cuda(x, weights, row_base, indices)
+    entry = _gather_entry("dlrm_interact_dot_forward_gather", x, weights)
     B, D = x.shape
     F = row_base.numel()
     npairs = F * (F + 1) // 2 if self_interaction else F * (F - 1) // 2
@@ -621,7 +638,7 @@ def interact_forward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: to
         raise ValueError("gather interaction: int32 indices [(F-1) * B] (one per bag)")
     if out is None:
         out = torch.empty(B, D + npairs, dtype=torch.float32, device=x.device)
-    _lib.call("dlrm_interact_dot_forward_gather", B, F, D, _p(x), x.stride(0), _p(weights),
+    _lib.call(entry, B, F, D, _p(x), x.stride(0), _p(weights),
               _p(row_base), _p(indices), int(self_interaction), _p(out), out.stride(0),
               _p(error_flag), _stream(x.device))
     return out
@@ -633,7 +650,8 @@ def interact_backward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: t
                              grad_x: Optional[torch.Tensor] = None,
                              grad_ly: Optional[torch.Tensor] = None, relu_x: bool = False):
     """Backward of interact_forward_gather (rows re-gathered; call before the embedding
-    update): grad_x [B, D] and grad_ly [B, T, D]."""
+    update): grad_x [B, D] and grad_ly [B, T, D].  fp16 ``weights`` as in the forward."""
+    entry = _gather_entry("dlrm_interact_dot_backward_gather", x, weights)
     B, D = x.shape
     T = row_base.numel() - 1
     if grad_x is None:
@@ -643,7 +661,7 @@ def interact_backward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: t
     gfeats, gstrides = feature_views(grad_x, grad_ly)
     gptrs, gbs = _feature_arrays(gfeats, gstrides)
     g = grad_out if grad_out.stride(1) == 1 else grad_out.contiguous()
-    _lib.call("dlrm_interact_dot_backward_gather", B, T + 1, D, _p(x), x.stride(0), _p(weights),
+    _lib.call(entry, B, T + 1, D, _p(x), x.stride(0), _p(weights),
               _p(row_base), _p(indices), int(self_interaction), _p(g), g.stride(0), gptrs, gbs,
               int(relu_x), _stream(x.device))
     return grad_x, grad_ly
@@ -1164,6 +1182,14 @@ def scale_(x: torch.Tensor, alpha: float) -> None:
 def uniform_fill_(out: torch.Tensor, lo: float, hi: float, seed: int) -> torch.Tensor:
     _lib.call("dlrm_uniform_fill", _p(out), out.numel(), float(lo), float(hi),
               int(seed) & 0xFFFFFFFFFFFFFFFF, _stream(out.device))
+    return out
+
+
+def uniform_fill_at_(out: torch.Tensor, lo: float, hi: float, seed: int,
+                     first: int) -> torch.Tensor:
+    """Elements [first, first + out.numel()) of uniform_fill_'s stream for ``seed``."""
+    _lib.call("dlrm_uniform_fill_at", _p(out), out.numel(), float(lo), float(hi),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), _stream(out.device))
     return out
 
 

@@ -23,6 +23,11 @@ optimizer update.  Layout decisions (MI355X-first):
 * Mixed precision on request (TrainerConfig.mlp_precision = "bf16"): the MLP layers below the
   head run forward, data gradient and weight gradient on the bf16 MFMA from the same fp32
   buffers (the 16-bit closures of DLRMTrainer._build); everything above stays as described.
+* fp16 tables on request (TrainerConfig.emb_precision = "fp16", one GPU, SGD): the row buffer
+  is [sum rows, D] half (C3: 13.9 GB); the gather-fused interaction and the pooled lookup
+  widen a row as they load it, the update rounds the new row to nearest even as it stores it
+  (no stochastic rounding: an update below half an fp16 ulp of the weight vanishes) and runs
+  as launches of its own; everything else of the step stays fp32.
 * Learning-rate schedule on request (TrainerConfig.lr_num_warmup_steps / lr_decay_start_step /
   lr_num_decay_steps, or device_lr): the step's rates live in device memory, a one-thread
   kernel at the head of the step advances the reference's LRPolicyScheduler and every update
@@ -99,6 +104,13 @@ class TrainerConfig:
     lr_decay_start_step: int = 0
     lr_num_decay_steps: int = 0
     device_lr: bool = False
+    # the embedding tables' storage: "fp32", or "fp16" = the row buffer held as [rows, D]
+    # half (the reference's --fbgemm-emb tables: FP16 weights with EXACT_SGD,
+    # dlrm_s_pytorch.py:337-366).  A row is widened to fp32 as it is loaded and the updated
+    # row is rounded to nearest even as it is stored; pooled embeddings, interaction,
+    # gradients and dense parameters stay fp32 (DESIGN.md §18 has the limits: SGD only, no
+    # QR tables, one GPU, D % 4 == 0 and D <= 512, no stochastic rounding)
+    emb_precision: str = "fp32"
 
     @property
     def lr_policy_steps(self):
@@ -118,6 +130,22 @@ class TrainerConfig:
                                       "(predict(..., precision='fp16') is available)")
         if self.mlp_precision not in ("fp32", "bf16"):
             raise ValueError(f"mlp_precision {self.mlp_precision!r}: 'fp32' or 'bf16'")
+        if self.emb_precision not in ("fp32", "fp16"):
+            raise ValueError(f"emb_precision {self.emb_precision!r}: 'fp32' or 'fp16'")
+        if self.emb_precision == "fp16":
+            if self.optimizer == "rwsadagrad":
+                raise NotImplementedError(
+                    "emb_precision='fp16' with optimizer='rwsadagrad': there is no fp16 "
+                    "row-wise Adagrad kernel (the reference's fp16 tables are EXACT_SGD only; "
+                    "DESIGN.md §18)")
+            if self.qr_flag:
+                raise NotImplementedError(
+                    "emb_precision='fp16' with qr_flag: the QR combine runs on fp32 tables "
+                    "only (DESIGN.md §18)")
+            if int(self.m_spa) % 4 or int(self.m_spa) > 512:
+                raise NotImplementedError(
+                    f"emb_precision='fp16' with m_spa={self.m_spa}: the fp16 lookup takes D a "
+                    "multiple of 4 and at most 512 (dlrm_tbe_forward_rows; DESIGN.md §18)")
 
 
 @dataclass
@@ -154,6 +182,11 @@ class DLRMTrainer:
         ``force_dist``: the multi-GPU schedule (all-to-all, gradient bucket, all-reduce)
         even at world_size 1, on a 1-rank group (its tests run RCCL on one GPU)."""
         self.cfg = cfg
+        self.emb_f16 = cfg.emb_precision == "fp16"
+        if self.emb_f16 and (world_size > 1 or force_dist):
+            raise NotImplementedError(
+                "emb_precision='fp16' on the multi-GPU schedule: the fp16 tables run on one "
+                "GPU only (DESIGN.md §18)")
         self.dev = torch.device(device)
         self.rank, self.world = rank, world_size
         self.pg = process_group
@@ -225,7 +258,8 @@ class DLRMTrainer:
         self.row_base = torch.tensor(self._row_bases, dtype=torch.int64, device=self.dev)
         self.total_rows = int(sum(rows))
         ops.check_tbe_rows(self.total_rows, "DLRMTrainer (this rank's tables)")
-        self.weights = torch.empty((max(self.total_rows, 1), D), dtype=torch.float32,
+        self.weights = torch.empty((max(self.total_rows, 1), D),
+                                   dtype=torch.float16 if self.emb_f16 else torch.float32,
                                    device=self.dev)
         self.momentum = None
         if cfg.optimizer == "rwsadagrad":
@@ -367,7 +401,9 @@ class DLRMTrainer:
             n = int(self.cfg.ln_emb[t])
             a = math.sqrt(1.0 / n)
             view = self.weights[self._rows(p)]
-            if self.phys_kind[p] == 0:
+            if self.emb_f16:  # the fp32 init of the same seed, rounded to nearest once
+                self._fill_f16(view, -a, a, seed * 1000003 + t)
+            elif self.phys_kind[p] == 0:
                 ops.uniform_fill_(view, -a, a, seed * 1000003 + t)
             else:  # QR tables: uniform [sqrt(1/n), 1] (tricks/qr_embedding_bag.py:153-154)
                 ops.uniform_fill_(view, a, 1.0, seed * 1000003 + t + 7919 * self.phys_kind[p])
@@ -379,8 +415,22 @@ class DLRMTrainer:
                 L.W[:, :L.K].normal_(0.0, math.sqrt(2.0 / (L.N + L.K)), generator=g)
                 L.b.normal_(0.0, math.sqrt(1.0 / L.N), generator=g)
 
+    _F16_INIT_CHUNK = 1 << 24  # fp32 elements staged per launch pair (64 MB)
+
+    def _fill_f16(self, view: torch.Tensor, lo: float, hi: float, seed: int) -> None:
+        """``view`` (fp16, contiguous rows) = uniform_fill_(fp32 of the same shape).half(),
+        staged through a bounded fp32 scratch: no second full-size buffer at any table size."""
+        flat = view.view(-1)
+        n = flat.numel()
+        scratch = torch.empty(min(n, self._F16_INIT_CHUNK), dtype=torch.float32, device=self.dev)
+        for o in range(0, n, self._F16_INIT_CHUNK):
+            m = min(self._F16_INIT_CHUNK, n - o)
+            ops.uniform_fill_at_(scratch[:m], lo, hi, seed, o)
+            flat[o:o + m].copy_(scratch[:m])  # fp32 -> fp16: round to nearest even
+
     def load_dense(self, mlp_params: Sequence[tuple], tables: Optional[Sequence] = None):
-        """Copy (W [N,K], b [N]) per layer (bottom then top) and optionally GLOBAL tables."""
+        """Copy (W [N,K], b [N]) per layer (bottom then top) and optionally GLOBAL tables
+        (emb_precision "fp16": each table rounded to nearest even once, by the copy)."""
         with torch.no_grad():
             for L, (W, b) in zip(self.layers, mlp_params):
                 L.W.zero_()
@@ -769,6 +819,11 @@ class DLRMTrainer:
         # the forward-only pass runs dlrm_tbe_forward: nothing of the backward's sort
         presort = train and self.tbe_presort
         gather = (presort or not train) and not dist and self._gather_applies(batch)
+        # fp16 tables (cfg.emb_precision): the same pieces on the fp16 row buffer - the
+        # gather-fused interaction reads half rows, the pooled lookup is dlrm_tbe_forward_rows
+        # and the update MODE_SGD_F16 as launches of its own (no fp16 launch role: tbe_role
+        # below is off for them)
+        f16 = self.emb_f16
         # The 16-bit step has no launch role, no bottom chain in the lookup launch and no
         # side-stream overlap (DESIGN.md §16 has the plan to give it them): they are switched
         # off here, once, and the pieces below take the branches they take in an fp32 step
@@ -843,7 +898,24 @@ class DLRMTrainer:
                     st["csr"] = self._phys_csr(batch, B)
                 idx, off = st["csr"]
                 out = bufs["P"] if self.qr_active else bufs["E"]
-                if presort:
+                if f16 and not gather:
+                    # the pooled lookup on fp16 rows is a launch of its own; the lookup launch
+                    # keeps its sort role (the sort never reads a row) and the bottom MLP's
+                    # where the per-table sort applies, else the backward sorts itself
+                    st["presorted"] = presort and self._presort_sorts(batch, idx, B)
+                    if st["presorted"]:
+                        ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B,
+                                                idx, off, self._ws_tbe(idx.numel()),
+                                                batch.max_per_table,
+                                                error_flag=self.tbe_error_flag, bottom=bottom,
+                                                lookup=False)
+                    elif bottom is not None:
+                        ops.mlp_chain_forward(bottom, self.dev)
+                    ops.tbe_forward_rows(self.weights, ops.ROWS_F16, D, self.row_base,
+                                         self.T_phys, B, idx, off, out=out,
+                                         out_batch_stride=out.stride(0),
+                                         error_flag=self.tbe_error_flag)
+                elif presort:
                     ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B, idx,
                                             off, self._ws_tbe(idx.numel()),
                                             batch.max_per_table, out=None if gather else out,
@@ -1182,6 +1254,8 @@ class DLRMTrainer:
             with prof("tbe_bwd"):
                 if self.T_local > 0:
                     mode = "rowwise_adagrad" if cfg.optimizer == "rwsadagrad" else "sgd"
+                    if f16:
+                        mode = "sgd_f16"
                     idx, off = st["csr"]
                     grad = bufs["dE"]
                     if self.qr_active:
@@ -1199,7 +1273,8 @@ class DLRMTrainer:
                               workspace=self._ws_tbe(idx.numel()),
                               max_lookups_per_table=batch.max_per_table,
                               error_flag=self.tbe_error_flag,
-                              presorted=ops.PRESORTED_ANY if s1 is not None else presort)
+                              presorted=ops.PRESORTED_ANY if s1 is not None
+                              else st.get("presorted", presort))
 
         @record_function("## Backward ##")
         def backward_single():  # one GPU: bottom backward || embedding backward
@@ -1385,6 +1460,15 @@ class DLRMTrainer:
                 and 0 < batch.max_per_table <= ops.TBE_PRESORT_SEG_CAP
                 and self.weights.shape[0] < 0xFFFFFFFF
                 and batch.indices.numel() == self.T * batch.X.shape[0])
+
+    def _presort_sorts(self, batch: Batch, idx: torch.Tensor, B: int) -> bool:
+        """Whether the lookup launch runs the backward's per-table sort for this batch
+        (dlrm_tbe_forward_presort's own rule: 32-bit row keys, every table within the LDS
+        sort's bound); its sort-only form exists only then."""
+        n = idx.numel()
+        return (0 < batch.max_per_table <= ops.TBE_PRESORT_SEG_CAP
+                and self.weights.shape[0] < 0xFFFFFFFF and 0 < n < 0x7FFFFFFF
+                and self.T_phys * B < 0x7FFFFFFF)
 
     def _phys_csr(self, batch: Batch, B: int):
         """(indices, offsets) of the physical tables for this batch: the batch's own CSR, or

@@ -124,8 +124,13 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 14: device-resident learning rates: dlrm_lr_state_* + dlrm_lr_schedule_tick (the reference's
  *    LRPolicyScheduler advanced by a one-thread kernel), a `_dev` sibling of every entry
  *    point that takes a learning rate (the rate read from device memory when the kernel
- *    runs), dlrm_gemm_problem.alpha_dev. */
-#define DLRM_ABI_VERSION 14 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    runs), dlrm_gemm_problem.alpha_dev.
+ * 15: fp16 embedding tables in the fused engine: dlrm_interact_dot_forward_gather_f16 /
+ *    _backward_gather_f16 (the gather-fused dot interaction reading fp16 rows) and
+ *    dlrm_tbe_backward_sgd_f16_dev (the fp16 exact-SGD update at a device-resident rate);
+ *    dlrm_uniform_fill_at (a window of dlrm_uniform_fill's stream: the fp16 tables' init is
+ *    staged through a bounded fp32 buffer). */
+#define DLRM_ABI_VERSION 15 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -527,6 +532,26 @@ int dlrm_interact_dot_backward_gather(int32_t B, int32_t F, int32_t D, const flo
                                       int64_t ld_gout, float* const* grad_ptrs,
                                       const int64_t* grad_bstrides, int32_t relu_x,
                                       dlrm_stream_t stream);
+/*
+ * ABI v15.  The two gather entry points on fp16 tables: `weights` is [total rows][D] fp16
+ * (IEEE binary16, the layout of DLRM_ROWS_F16 and dlrm_tbe_backward_sgd_f16), 8-byte aligned
+ * (a lane reads its four columns as one 8-byte load).  Each row is widened to fp32 as it is
+ * loaded, which is exact, and everything after the load is the fp32 kernel: x, the output,
+ * the gradients and the arithmetic stay fp32, so the result is bitwise that of the fp32 entry
+ * point on the same values held as fp32.  Same dispatch, limits, error flag and statuses.
+ */
+int dlrm_interact_dot_forward_gather_f16(int32_t B, int32_t F, int32_t D, const float* x,
+                                         int64_t x_bstride, const void* weights,
+                                         const int64_t* row_base, const int32_t* indices,
+                                         int32_t self_interaction, float* out, int64_t ld_out,
+                                         int32_t* error_flag, dlrm_stream_t stream);
+int dlrm_interact_dot_backward_gather_f16(int32_t B, int32_t F, int32_t D, const float* x,
+                                          int64_t x_bstride, const void* weights,
+                                          const int64_t* row_base, const int32_t* indices,
+                                          int32_t self_interaction, const float* grad_out,
+                                          int64_t ld_gout, float* const* grad_ptrs,
+                                          const int64_t* grad_bstrides, int32_t relu_x,
+                                          dlrm_stream_t stream);
 /* Cat: out[b][f*D:(f+1)*D] = feature f. */
 int dlrm_interact_cat_forward(int32_t B, int32_t F, int32_t D, const float* const* feat_ptrs,
                               const int64_t* feat_bstrides, float* out, int64_t ld_out,
@@ -721,6 +746,10 @@ int dlrm_relu_backward(int64_t M, int64_t K, const float* dy, int64_t lddy, cons
 /* out[i] = lo + (hi - lo) * u_i, u_i uniform in [0,1) from a counter hash of (seed, i). */
 int dlrm_uniform_fill(float* out, int64_t n, float lo, float hi, uint64_t seed,
                       dlrm_stream_t stream);
+/* ABI v15: elements [first, first + n) of the same stream (out[i] takes u_{first + i}), for a
+ * caller that stages a long fill through a bounded buffer. */
+int dlrm_uniform_fill_at(float* out, int64_t n, float lo, float hi, uint64_t seed,
+                         int64_t first, dlrm_stream_t stream);
 /* Integer uniform draws in [0, hi) for synthetic indices (int32 or int64 out). */
 int dlrm_uniform_int_fill(void* out, int32_t out_bits, int64_t n, int64_t hi, uint64_t seed,
                           dlrm_stream_t stream);
@@ -958,6 +987,15 @@ int dlrm_tbe_backward_sgd_dev(float* weights, int64_t D, const int64_t* row_base
                               const float* lr_dev, int64_t max_lookups_per_table,
                               void* workspace, size_t workspace_bytes, int32_t* error_flag,
                               int32_t presorted, dlrm_stream_t stream);
+/* ABI v15: dlrm_tbe_backward_sgd_f16 at a device-resident rate. */
+int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int64_t* row_base, int32_t T,
+                                  int32_t B, const void* indices, int32_t index_bits,
+                                  const void* offsets, int32_t offset_bits, int64_t num_lookups,
+                                  int64_t total_rows, const float* per_sample_weights,
+                                  const float* grad_out, int64_t grad_batch_stride,
+                                  const float* lr_dev, int64_t max_lookups_per_table,
+                                  void* workspace, size_t workspace_bytes, int32_t* error_flag,
+                                  int32_t presorted, dlrm_stream_t stream);
 int dlrm_tbe_backward_rowwise_adagrad_dev(float* weights, float* momentum, int64_t D,
                                           const int64_t* row_base, int32_t T, int32_t B,
                                           const void* indices, int32_t index_bits,
