@@ -807,7 +807,7 @@ def colsum(Y: torch.Tensor, scale: Optional[torch.Tensor] = None, alpha: float =
     """``lr``: a float or a 1-element fp32 device tensor."""
     M, N = Y.shape
     need = _lib.query("dlrm_colsum_workspace_size", M, N)
-    if workspace is None or workspace.numel() < need:
+    if workspace is None:  # (a caller's own buffer is never swapped: too small is refused)
         workspace = _ws("colsum", need, Y.device)
     lr_dev = _lr_dev(lr, "colsum: lr")
     _lib.call("dlrm_colsum_f32" if lr_dev is None else "dlrm_colsum_f32_dev", M, N, _p(Y),
@@ -825,7 +825,7 @@ def head_forward_backward(X: torch.Tensor, w: torch.Tensor, b: Optional[torch.Te
                           workspace: Optional[torch.Tensor] = None):
     M, K = X.shape
     need = _lib.query("dlrm_head_workspace_size", M)
-    if workspace is None or workspace.numel() < need:
+    if workspace is None:  # (a caller's own buffer is never swapped: too small is refused)
         workspace = _ws("head", need, X.device)
     _lib.call("dlrm_head_forward_backward", M, K, _p(X), X.stride(0), _p(w), _p(b), _p(target),
               LOSS_BCE if loss == "bce" else LOSS_MSE, float(clamp_lo), float(grad_scale),
@@ -846,7 +846,7 @@ def head_step(X: torch.Tensor, w: torch.Tensor, target: torch.Tensor, loss: str 
     float or a 1-element fp32 device tensor (read by the update's launch when it runs)."""
     M, K = X.shape
     need = _lib.query("dlrm_head_step_workspace_size", M, K)
-    if workspace is None or workspace.numel() < need:
+    if workspace is None:  # (a caller's own buffer is never swapped: too small is refused)
         workspace = _ws("head_step", need, X.device)
     _check_cuda(X, w, target)
     lr_dev = _lr_dev(lr, "head_step: lr")
