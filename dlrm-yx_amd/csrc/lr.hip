@@ -1,7 +1,8 @@
 // Device-resident learning rates (ABI v14): the dlrm_lr_state block and the one-thread
 // kernel that advances the reference's LRPolicyScheduler (dlrm_s_pytorch.py:188-222) on the
 // device, so a replayed hipGraph walks the schedule with no host work.  Every update kernel
-// reads its rate from the block's lr[] slots (the `_dev` entry points).
+// reads its rate from the block's lr[] slots (the `_dev` entry points).  The fp16 tables'
+// stochastic-rounding state (ABI v16) and its one-thread tick live here too.
 //
 // The arithmetic is fp64 in the reference's operation order with IEEE division (this file
 // is built without any fast-math flag): lr[k] has the bits the host gets from
@@ -58,7 +59,23 @@ __global__ __launch_bounds__(64) void lr_tick_kernel(LrState* __restrict__ s) {
   s->step_count = sc + 1;
 }
 
+// dlrm_sr_state (ABI v16): uint64 seed, uint64 step; the update kernels only read it, so a
+// replayed graph of {update, tick} draws a fresh stream every step with no host work.
+static_assert(DLRM_SR_STATE_BYTES == 2 * sizeof(uint64_t), "dlrm_sr_state layout");
+__global__ __launch_bounds__(64) void sr_tick_kernel(uint64_t* __restrict__ s) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  s[1] = s[1] + 1;
+}
+
 }  // namespace
+
+extern "C" int dlrm_sr_tick(uint64_t* sr_state, dlrm_stream_t stream) {
+  DLRM_ARG(sr_state && (reinterpret_cast<uintptr_t>(sr_state) & 7) == 0,
+           "dlrm_sr_tick: sr_state must be an 8-byte aligned device pointer");
+  hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(1), 0, dlrm::as_stream(stream), sr_state);
+  DLRM_LAUNCH_CHECK("dlrm_sr_tick");
+  return DLRM_OK;
+}
 
 extern "C" size_t dlrm_lr_state_bytes(void) { return sizeof(LrState); }
 

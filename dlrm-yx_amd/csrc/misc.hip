@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "head_roles.hpp"
 #include "head_row.hpp"
+#include "splitmix.hpp"
 #include "tbe_bwd_roles.hpp"
 
 namespace {
@@ -256,13 +257,6 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(int64_t M, int64_t K,
     const int64_t m = j / K, k = j - m * K;
     dx[m * lddx + k] = y[m * ldy + k] > 0.f ? dy[m * lddy + k] : 0.f;
   }
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 // Element j of the call is element first + j of the seed's stream (first = 0: the whole

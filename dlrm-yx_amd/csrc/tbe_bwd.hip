@@ -896,7 +896,8 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
                const void* idx, const void* off, int64_t N, int64_t total_rows, const float* psw,
                const float* gout, int64_t gbs, float lr, const float* lr_dev, float eps, void* ws,
                size_t ws_bytes, int64_t max_seg, int32_t* err, int presorted, LaunchRole* defer,
-               hipStream_t st, const char* name, bool sort_only = false) {
+               hipStream_t st, const char* name, bool sort_only = false,
+               const uint64_t* sr_state = nullptr) {
   if (defer) {  // until proven fusable: nothing deferred
     *defer = LaunchRole{};
     defer->magic = kRoleMagic;
@@ -985,8 +986,9 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
 
   if (sort_only) return DLRM_OK;
 
+  const bool f16_rows = mode == MODE_SGD_F16 || mode == MODE_SGD_F16_SR;
   const bool vec4 = (D % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(W) & (mode == MODE_SGD_F16 ? 7 : 15)) == 0) &&
+                    ((reinterpret_cast<uintptr_t>(W) & (f16_rows ? 7 : 15)) == 0) &&
                     ((reinterpret_cast<uintptr_t>(gout) & 15) == 0) && (gbs % 4 == 0);
   const int64_t nchunks = vec4 ? D / 4 : D;
   int lpb = 1;
@@ -1032,14 +1034,14 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
       hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, true>), dim3(blocks),  \
                          dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out,                \
                          per_table ? w.bag_of : w.pos_out, psw, gout, gbs, N, lr, eps,         \
-                         sentinel, w.partial, ch, lr_dev);                                     \
+                         sentinel, w.partial, ch, lr_dev, sr_state);                           \
     else                                                                                       \
       hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, false>), dim3(blocks), \
                          dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out, w.bag_of, psw, \
-                         gout, gbs, N, lr, eps, sentinel, w.partial, ch, lr_dev);              \
+                         gout, gbs, N, lr, eps, sentinel, w.partial, ch, lr_dev, sr_state);    \
     hipLaunchKernelGGL((tbe_bwd_combine_kernel<LPB, VW, MV, KeyT, MODE>), dim3(blocks),        \
                        dim3(256), 0, st, W, mom, D, w.keys_out, N, lr, eps, sentinel,          \
-                       w.partial, ch, lr_dev);                                                 \
+                       w.partial, ch, lr_dev, sr_state);                                       \
   } while (0)
 #define BY_LPB(VW, MODE)                             \
   switch (lpb) {                                     \
@@ -1062,6 +1064,8 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
     BY_LPB(VW, MODE_ADAGRAD)           \
   } else if (mode == MODE_SGD_F16) {   \
     BY_LPB(VW, MODE_SGD_F16)           \
+  } else if (mode == MODE_SGD_F16_SR) {\
+    BY_LPB(VW, MODE_SGD_F16_SR)        \
   } else {                             \
     BY_LPB(VW, MODE_DENSE)             \
   }
@@ -1082,7 +1086,8 @@ int bwd_dispatch(int mode, float* W, float* mom, int64_t D, const int64_t* row_b
                  int64_t total_rows, const float* psw, const float* gout, int64_t gbs, float lr,
                  float eps, void* ws, size_t ws_bytes, int64_t max_seg, int32_t* err,
                  int presorted, LaunchRole* defer, dlrm_stream_t stream, const char* name,
-                 bool sort_only = false, const float* lr_dev = nullptr) {
+                 bool sort_only = false, const float* lr_dev = nullptr,
+                 const uint64_t* sr_state = nullptr) {
   DLRM_ARG(((W && gout) || sort_only) && row_base && (N == 0 || (idx && off)),
            "%s: null pointer", name);
   DLRM_ARG(presorted >= 0 && presorted <= DLRM_PRESORTED_ANY, "%s: bad presorted %d", name,
@@ -1102,7 +1107,7 @@ int bwd_dispatch(int mode, float* W, float* mom, int64_t D, const int64_t* row_b
 #define BWD(K, I, O)                                                                     \
   return launch_bwd<K, I, O>(mode, W, mom, D, row_base, T, B, idx, off, N, total_rows, psw, \
                              gout, gbs, lr, lr_dev, eps, ws, ws_bytes, max_seg, err, presorted, \
-                             defer, st, name, sort_only)
+                             defer, st, name, sort_only, sr_state)
   if (ib == 32 && ob == 32) BWD(uint32_t, int32_t, int32_t);
   if (ib == 32 && ob == 64) BWD(uint32_t, int32_t, int64_t);
   if (ib == 64 && ob == 32) BWD(uint32_t, int64_t, int32_t);
@@ -1187,6 +1192,29 @@ extern "C" int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int
                       per_sample_weights, grad_out, grad_batch_stride, 0.f, 0.f, workspace,
                       workspace_bytes, max_lookups_per_table, error_flag, presorted, nullptr, stream,
                       "dlrm_tbe_backward_sgd_f16_dev", false, lr_dev);
+}
+
+// ABI v16: the fp16 update with the store rounded stochastically; the stream's (seed, step)
+// is read from sr_state when the kernels run, and advanced by dlrm_sr_tick only.
+extern "C" int dlrm_tbe_backward_sgd_f16_sr(void* weights, int64_t D, const int64_t* row_base,
+                                            int32_t T, int32_t B, const void* indices,
+                                            int32_t index_bits, const void* offsets,
+                                            int32_t offset_bits, int64_t num_lookups,
+                                            int64_t total_rows, const float* per_sample_weights,
+                                            const float* grad_out, int64_t grad_batch_stride,
+                                            float lr, const float* lr_dev,
+                                            const uint64_t* sr_state,
+                                            int64_t max_lookups_per_table, void* workspace,
+                                            size_t workspace_bytes, int32_t* error_flag,
+                                            int32_t presorted, dlrm_stream_t stream) {
+  const char* name = "dlrm_tbe_backward_sgd_f16_sr";
+  DLRM_ARG(sr_state && (reinterpret_cast<uintptr_t>(sr_state) & 7) == 0,
+           "%s: sr_state must be an 8-byte aligned device pointer", name);
+  return bwd_dispatch(MODE_SGD_F16_SR, static_cast<float*>(weights), nullptr, D, row_base, T, B,
+                      indices, index_bits, offsets, offset_bits, num_lookups, total_rows,
+                      per_sample_weights, grad_out, grad_batch_stride, lr_dev ? 0.f : lr, 0.f,
+                      workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted,
+                      nullptr, stream, name, false, lr_dev, sr_state);
 }
 
 extern "C" int dlrm_tbe_backward_rowwise_adagrad(

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "head_roles.hpp"
+#include "splitmix.hpp"
 #include "tbe_common.hpp"
 #include "tbe_sort.hpp"
 
@@ -19,13 +20,19 @@ constexpr int64_t kLongChN = 1 << 18;
 
 // MODE_SGD_F16: exact SGD on fp16 weights (the fbgemm TBE's FP16 tables): the row is read
 // as fp16, updated in fp32 and stored back rounded to nearest even.
-enum { MODE_SGD = 0, MODE_ADAGRAD = 1, MODE_DENSE = 2, MODE_SGD_F16 = 3 };
+// MODE_SGD_F16_SR: the same update in every respect but the store, which rounds
+// stochastically (sr16_bits) with the element's draw of the call's (seed, step) stream.
+enum { MODE_SGD = 0, MODE_ADAGRAD = 1, MODE_DENSE = 2, MODE_SGD_F16 = 3, MODE_SGD_F16_SR = 4 };
+template <int MODE>
+constexpr bool kF16Rows = MODE == MODE_SGD_F16 || MODE == MODE_SGD_F16_SR;
+template <int MODE>
+constexpr bool kSgdMode = MODE == MODE_SGD || kF16Rows<MODE>;
 
 // Weight-row element access by mode: fp32 rows, or fp16 rows (W then points at halves).
 template <int MODE, int VW>
 __device__ __forceinline__ typename VecT<VW>::T wload(const float* __restrict__ W, int64_t row,
                                                       int64_t D, int chunk) {
-  if constexpr (MODE == MODE_SGD_F16) {
+  if constexpr (kF16Rows<MODE>) {
     const _Float16* h = reinterpret_cast<const _Float16*>(W) + row * D + (int64_t)chunk * VW;
     if constexpr (VW == 4) {
       const uint2 u = *reinterpret_cast<const uint2*>(h);
@@ -41,10 +48,27 @@ __device__ __forceinline__ typename VecT<VW>::T wload(const float* __restrict__ 
   }
 }
 
+// sr: the call's stochastic-rounding key (sr_load_key; MODE_SGD_F16_SR only, else unused)
 template <int MODE, int VW>
 __device__ __forceinline__ void wstore(float* __restrict__ W, int64_t row, int64_t D, int chunk,
-                                       const typename VecT<VW>::T& v) {
-  if constexpr (MODE == MODE_SGD_F16) {
+                                       const typename VecT<VW>::T& v, uint64_t sr) {
+  if constexpr (MODE == MODE_SGD_F16_SR) {
+    _Float16* h = reinterpret_cast<_Float16*>(W) + row * D + (int64_t)chunk * VW;
+    const uint64_t chunks4 = (uint64_t)((D + 3) >> 2);
+    if constexpr (VW == 4) {
+      // one hash serves the four columns this lane holds
+      const uint64_t x = sr_word(sr, (uint64_t)row, chunks4, (uint64_t)chunk);
+      const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+      uint2 u;
+      u.x = sr16_bits(v.x, lo & 0xffffu) | (sr16_bits(v.y, lo >> 16) << 16);
+      u.y = sr16_bits(v.z, hi & 0xffffu) | (sr16_bits(v.w, hi >> 16) << 16);
+      *reinterpret_cast<uint2*>(h) = u;
+    } else {
+      const uint64_t x = sr_word(sr, (uint64_t)row, chunks4, (uint64_t)(chunk >> 2));
+      const uint32_t r = (uint32_t)(x >> (16 * (chunk & 3))) & 0xffffu;
+      h[0] = __builtin_bit_cast(_Float16, (unsigned short)sr16_bits(v, r));
+    }
+  } else if constexpr (MODE == MODE_SGD_F16) {
     _Float16* h = reinterpret_cast<_Float16*>(W) + row * D + (int64_t)chunk * VW;
     if constexpr (VW == 4) {
       auto bits = [](float f) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f); };
@@ -65,17 +89,17 @@ template <int LPB, int VW, int MAXV, int MODE>
 __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __restrict__ mom,
                                              int64_t D, int64_t row,
                                              typename VecT<VW>::T (&g)[MAXV], int gl,
-                                             int nchunks, float lr, float eps) {
+                                             int nchunks, float lr, float eps, uint64_t sr) {
   using V = typename VecT<VW>::T;
   V* wrow = reinterpret_cast<V*>(W + row * D);
-  if (MODE == MODE_SGD || MODE == MODE_SGD_F16) {
+  if (kSgdMode<MODE>) {
 #pragma unroll
     for (int c = 0; c < MAXV; ++c) {
       const int chunk = gl + c * LPB;
       if (chunk < nchunks) {
         V w = wload<MODE, VW>(W, row, D, chunk);
         vfma(w, -lr, g[c]);
-        wstore<MODE, VW>(W, row, D, chunk, w);
+        wstore<MODE, VW>(W, row, D, chunk, w, sr);
       }
     }
   } else if (MODE == MODE_DENSE) {
@@ -126,17 +150,18 @@ __device__ __forceinline__ void finalize_row_pf(float* __restrict__ W, float* __
                                                 int64_t D, int64_t row,
                                                 typename VecT<VW>::T (&g)[MAXV],
                                                 typename VecT<VW>::T (&w)[MAXV], float m0,
-                                                int gl, int nchunks, float lr, float eps) {
+                                                int gl, int nchunks, float lr, float eps,
+                                                uint64_t sr) {
   using V = typename VecT<VW>::T;
   V* wrow = reinterpret_cast<V*>(W + row * D);
-  if (MODE == MODE_SGD || MODE == MODE_SGD_F16) {
+  if (kSgdMode<MODE>) {
 #pragma unroll
     for (int c = 0; c < MAXV; ++c) {
       const int chunk = gl + c * LPB;
       if (chunk < nchunks) {
         V x = w[c];
         vfma(x, -lr, g[c]);
-        wstore<MODE, VW>(W, row, D, chunk, x);
+        wstore<MODE, VW>(W, row, D, chunk, x, sr);
       }
     }
   } else if (MODE == MODE_DENSE) {
@@ -194,7 +219,7 @@ __device__ __forceinline__ void tbe_bwd_block_body(
     const KeyT* __restrict__ keys, const int32_t* __restrict__ pos,
     const int32_t* __restrict__ bag_of, const float* __restrict__ psw,
     const float* __restrict__ gout, int64_t gbs, int64_t N, float lr, float eps,
-    KeyT sentinel, float* __restrict__ partial, int ch, int blk, int nblk) {
+    KeyT sentinel, float* __restrict__ partial, int ch, int blk, int nblk, uint64_t sr = 0) {
   using V = typename VecT<VW>::T;
   constexpr int GPW = kWave / LPB;
   const int lane = threadIdx.x & (kWave - 1);
@@ -240,9 +265,10 @@ __device__ __forceinline__ void tbe_bwd_block_body(
       if (starts && ends) {
         if constexpr (PF)
           finalize_row_pf<LPB, VW, MAXV, MODE>(W, mom, D, (int64_t)cur, acc, wcur, mcur, gl,
-                                               nchunks, lr, eps);
+                                               nchunks, lr, eps, sr);
         else
-          finalize_row<LPB, VW, MAXV, MODE>(W, mom, D, (int64_t)cur, acc, gl, nchunks, lr, eps);
+          finalize_row<LPB, VW, MAXV, MODE>(W, mom, D, (int64_t)cur, acc, gl, nchunks, lr, eps,
+                                            sr);
       } else {
         V* dst = reinterpret_cast<V*>(partial + (2 * k + (seg_a == i0 ? 0 : 1)) * D);
 #pragma unroll
@@ -367,7 +393,7 @@ template <int LPB, int VW, int MAXV, typename KeyT, int MODE, int NF0 = 16>
 __device__ __forceinline__ void tbe_bwd_combine_body(
     float* __restrict__ W, float* __restrict__ mom, int64_t D, const KeyT* __restrict__ keys,
     int64_t N, float lr, float eps, KeyT sentinel, const float* __restrict__ partial, int ch,
-    int blk, int nblk) {
+    int blk, int nblk, uint64_t sr = 0) {
   using V = typename VecT<VW>::T;
   constexpr int GPW = kWave / LPB;
   const int lane = threadIdx.x & (kWave - 1);
@@ -455,7 +481,7 @@ __device__ __forceinline__ void tbe_bwd_combine_body(
     }
 #pragma unroll
     for (int c = 0; c < MAXV; ++c) vsub(acc[c], comp[c]);  // fold the compensation back in
-    finalize_row<LPB, VW, MAXV, MODE>(W, mom, D, (int64_t)last, acc, gl, nchunks, lr, eps);
+    finalize_row<LPB, VW, MAXV, MODE>(W, mom, D, (int64_t)last, acc, gl, nchunks, lr, eps, sr);
   }
 }
 
@@ -467,20 +493,26 @@ __global__ __launch_bounds__(256) void tbe_bwd_block_kernel(
     const KeyT* __restrict__ keys, const int32_t* __restrict__ pos,
     const int32_t* __restrict__ bag_of, const float* __restrict__ psw,
     const float* __restrict__ gout, int64_t gbs, int64_t N, float lr, float eps,
-    KeyT sentinel, float* __restrict__ partial, int ch, const float* __restrict__ lr_dev) {
+    KeyT sentinel, float* __restrict__ partial, int ch, const float* __restrict__ lr_dev,
+    const uint64_t* __restrict__ sr_state) {
+  uint64_t sr = 0;
+  if constexpr (MODE == MODE_SGD_F16_SR) sr = sr_load_key(sr_state);
   tbe_bwd_block_body<LPB, VW, MAXV, KeyT, MODE, SB>(W, mom, D, B, keys, pos, bag_of, psw, gout,
                                                     gbs, N, dlrm_resolve_lr(lr_dev, lr), eps,
-                                                    sentinel, partial, ch, blockIdx.x, gridDim.x);
+                                                    sentinel, partial, ch, blockIdx.x, gridDim.x,
+                                                    sr);
 }
 
 template <int LPB, int VW, int MAXV, typename KeyT, int MODE>
 __global__ __launch_bounds__(256) void tbe_bwd_combine_kernel(
     float* __restrict__ W, float* __restrict__ mom, int64_t D, const KeyT* __restrict__ keys,
     int64_t N, float lr, float eps, KeyT sentinel, const float* __restrict__ partial, int ch,
-    const float* __restrict__ lr_dev) {
+    const float* __restrict__ lr_dev, const uint64_t* __restrict__ sr_state) {
+  uint64_t sr = 0;
+  if constexpr (MODE == MODE_SGD_F16_SR) sr = sr_load_key(sr_state);
   tbe_bwd_combine_body<LPB, VW, MAXV, KeyT, MODE>(W, mom, D, keys, N,
                                                   dlrm_resolve_lr(lr_dev, lr), eps, sentinel,
-                                                  partial, ch, blockIdx.x, gridDim.x);
+                                                  partial, ch, blockIdx.x, gridDim.x, sr);
 }
 
 // ------------------------------------------------------------ deferred update --

@@ -137,7 +137,9 @@ class DLRM_Net(nn.Module):
     def create_emb_fbgemm(self, Ds, Es, weighted_pooling=None):
         """dlrm_s_pytorch.py:337-366: one FP16-weight TBE over the local tables with exact
         SGD fused (modules.SplitTableBatchedEmbeddingBags; fbgemm's default learning rate
-        0.01, eps 0.01 as the reference passes it)."""
+        0.01, eps 0.01 as the reference passes it).  The reference passes no
+        stochastic_rounding, and fbgemm defaults it to True: fbgemm_stochastic_rounding=True
+        is the closer stand-in for its run (the stream is seeded from torch.initial_seed())."""
         T = len(Es)
         emb_indices = ([i for i in range(T) if i in self.local_emb_indices]
                        if ext_dist.my_size > 1 else list(range(T)))
@@ -148,8 +150,9 @@ class DLRM_Net(nn.Module):
                               size=(int(Es[i]), int(Ds[i]))).astype(np.float32)
                   for i in emb_indices]
         return SplitTableBatchedEmbeddingBags([(int(Es[i]), int(Ds[i])) for i in emb_indices],
-                                              learning_rate=0.01, eps=0.01,
-                                              tables=tables), [None] * T
+                                              learning_rate=0.01, eps=0.01, tables=tables,
+                                              stochastic_rounding=self.fbgemm_stochastic_rounding,
+                                              seed=torch.initial_seed()), [None] * T
 
     def __init__(self, m_spa=None, ln_emb=None, ln_bot=None, ln_top=None,
                  arch_interaction_op=None, arch_interaction_itself=False, sigmoid_bot=-1,
@@ -157,7 +160,7 @@ class DLRM_Net(nn.Module):
                  qr_flag=False, qr_operation="mult", qr_collisions=0, qr_threshold=200,
                  md_flag=False, md_threshold=200, weighted_pooling=None, loss_function="bce",
                  batched_emb=False, fbgemm_emb=False, load_processed=False, sharder="naive",
-                 allocation=None):
+                 allocation=None, fbgemm_stochastic_rounding=False):
         super().__init__()
         if (m_spa is None or ln_emb is None or ln_bot is None or ln_top is None or
                 arch_interaction_op is None):
@@ -190,6 +193,7 @@ class DLRM_Net(nn.Module):
             self.md_threshold = md_threshold
         self.batched_emb = batched_emb
         self.fbgemm_emb = fbgemm_emb
+        self.fbgemm_stochastic_rounding = bool(fbgemm_stochastic_rounding)
         self.load_processed = load_processed
         self.sharder = sharder
         self.local_emb_indices = list(range(len(self.ln_emb)))

@@ -195,12 +195,17 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
 
     Forward: dlrm_tbe_forward_rows (F16 rows, fp32 accumulation).  Backward:
     dlrm_tbe_backward_sgd_f16 (deterministic per-row fp32 gradient sum, round-to-nearest
-    fp16 store).  fbgemm_gpu itself is not in the reference tree, so its init bound, its
-    LFU cache and its stochastic rounding are not reproduced (parity unpinned against it);
-    tables are drawn U(+-sqrt(1/n)) like the other DLRM paths."""
+    fp16 store).  ``stochastic_rounding=True`` (fbgemm's default, so what the reference's run
+    does): the store is rounded stochastically instead (dlrm_tbe_backward_sgd_f16_sr) from
+    the counter-based stream of (``seed``, step, row, column) - the module owns the device
+    state (the ``sr_state`` buffer, in its state_dict) and ticks it after each fused update.
+    fbgemm_gpu itself is not in the reference tree, so its init bound, its LFU cache and
+    its random stream are not reproduced (parity unpinned against it); tables are drawn
+    U(+-sqrt(1/n)) like the other DLRM paths."""
 
     def __init__(self, embedding_specs, learning_rate: float = 0.01, eps: float = 1.0e-8,
-                 tables=None, seed: int = 0, device=None, **unused):
+                 tables=None, seed: int = 0, device=None, stochastic_rounding: bool = False,
+                 **unused):
         super().__init__()
         Es = [int(e) for e, *_ in embedding_specs]
         Ds = {int(d) for _, d, *_ in embedding_specs}
@@ -228,6 +233,10 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
         self.weights = Parameter(w.half(), requires_grad=True)
         self.register_buffer("table_offsets", torch.tensor([0] + [b for _, b in self.row_ranges],
                                                            dtype=torch.int64))
+        self.stochastic_rounding = bool(stochastic_rounding)
+        if self.stochastic_rounding:  # dlrm_sr_state: the uint64 bits of (seed, step = 0)
+            self.register_buffer("sr_state", torch.tensor([ops._as_i64(seed), 0],
+                                                          dtype=torch.int64))
         self.grad_mode = "fused"
         if device is not None:
             self.to(device)
@@ -241,6 +250,12 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
         return self.table_offsets
 
     def fused_update(self, indices, offsets, grad, psw, B):
+        if self.stochastic_rounding:
+            ops.tbe_backward("sgd", self.weights.data, self.table_offsets, self.T, B, indices,
+                             offsets, grad, lr=self.learning_rate, per_sample_weights=psw,
+                             sr_state=self.sr_state)
+            ops.sr_tick(self.sr_state)
+            return
         ops.tbe_backward("sgd", self.weights.data, self.table_offsets, self.T, B, indices,
                          offsets, grad, lr=self.learning_rate, per_sample_weights=psw)
 

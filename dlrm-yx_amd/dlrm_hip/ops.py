@@ -361,7 +361,8 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
                  grad_batch_stride: Optional[int] = None,
                  workspace: Optional[torch.Tensor] = None,
                  max_lookups_per_table: int = 0,
-                 error_flag: Optional[torch.Tensor] = None, presorted: int = False) -> None:
+                 error_flag: Optional[torch.Tensor] = None, presorted: int = False,
+                 sr_state: Optional[torch.Tensor] = None) -> None:
     """mode: 'sgd' (fused exact SGD; fp32 or fp16 weights; 'sgd_f16' names the fp16 case and
     refuses fp32 weights), 'rowwise_adagrad' (fused
     RWSAdagrad) or 'dense' (weights is a gradient buffer to accumulate into).  max_lookups_per_table:
@@ -370,9 +371,15 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     int32 that receives TBE_ERR_INDEX / TBE_ERR_TABLE_CAP bits (see check_tbe_errors).
     ``presorted``: True - the per-table sort ran in tbe_forward_presort; PRESORTED_ANY -
     tbe_backward_sort ran for this batch.  ``lr``: a float, or ('sgd', fp32 or fp16
-    weights, and 'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run."""
+    weights, and 'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run.
+    ``sr_state`` (fp16 weights only; ops.sr_state): the updated row is stored rounded
+    stochastically with the state's (seed, step) stream instead of to nearest even
+    (dlrm_tbe_backward_sgd_f16_sr); the state is read when the kernels run, never written."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     lr_dev = _lr_dev(lr, "tbe_backward: lr")
+    if sr_state is not None and not (mode in ("sgd", "sgd_f16")
+                                     and weights.dtype == torch.float16):
+        raise ValueError("tbe_backward: sr_state goes with 'sgd' / 'sgd_f16' on fp16 weights")
     D = weights.shape[1]
     N = indices.numel()
     total_rows = weights.shape[0]
@@ -388,7 +395,12 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     mx = int(max_lookups_per_table)
     if mode == "sgd_f16" and weights.dtype != torch.float16:
         raise ValueError("tbe_backward: mode 'sgd_f16' takes fp16 weights")
-    if mode in ("sgd", "sgd_f16") and weights.dtype == torch.float16:
+    if sr_state is not None:
+        _lib.call("dlrm_tbe_backward_sgd_f16_sr", _p(weights), *args_common,
+                  0.0 if lr_dev is not None else lr, lr_dev,
+                  _sr_ptr(sr_state, "tbe_backward"), mx, _p(workspace), workspace.numel(),
+                  _p(error_flag), int(presorted), st)
+    elif mode in ("sgd", "sgd_f16") and weights.dtype == torch.float16:
         if lr_dev is not None:
             _lib.call("dlrm_tbe_backward_sgd_f16_dev", _p(weights), *args_common, lr_dev, mx,
                       _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
@@ -1172,6 +1184,44 @@ def lr_schedule_tick(state: LRState) -> None:
     """One launch of one thread (dlrm_lr_schedule_tick): every slot's rate for the current
     step count, then step count + 1.  Enqueues only; capturable."""
     _lib.call("dlrm_lr_schedule_tick", _p(state.buf), _stream(state.buf.device))
+
+
+# ------------------------------- stochastic rounding of the fp16 tables' update ----
+_U64 = (1 << 64) - 1
+
+
+def _as_i64(v: int) -> int:
+    """The uint64 ``v`` (mod 2^64) as the int64 with the same bits."""
+    v = int(v) & _U64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def sr_state(seed: int = 0, step: int = 0, device=None) -> torch.Tensor:
+    """The dlrm_sr_state block (include/dlrm_hip.h) in device memory: a 2-element int64
+    tensor holding the uint64 bits of (seed, step).  tbe_backward('sgd_f16', ...,
+    sr_state=) reads it when its kernels run; sr_tick advances the step."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return torch.tensor([_as_i64(seed), _as_i64(step)], dtype=torch.int64).to(dev)
+
+
+def sr_state_values(state: torch.Tensor):
+    """(seed, step) of an sr_state tensor as unsigned Python ints; synchronises."""
+    s, t = (int(v) & _U64 for v in state.view(torch.int64).cpu().tolist())
+    return s, t
+
+
+def _sr_ptr(state: torch.Tensor, who: str):
+    u64 = getattr(torch, "uint64", None)
+    if (not isinstance(state, torch.Tensor) or not state.is_cuda or state.numel() != 2
+            or state.dtype not in (torch.int64, u64) or not state.is_contiguous()):
+        raise ValueError(f"{who}: sr_state is a contiguous 2-element int64/uint64 device "
+                         "tensor (ops.sr_state)")
+    return _p(state)
+
+
+def sr_tick(state: torch.Tensor) -> None:
+    """One launch of one thread (dlrm_sr_tick): step += 1.  Enqueues only; capturable."""
+    _lib.call("dlrm_sr_tick", _sr_ptr(state, "sr_tick"), _stream(state.device))
 
 
 def scale_(x: torch.Tensor, alpha: float) -> None:

@@ -26,8 +26,9 @@ optimizer update.  Layout decisions (MI355X-first):
 * fp16 tables on request (TrainerConfig.emb_precision = "fp16", one GPU, SGD): the row buffer
   is [sum rows, D] half (C3: 13.9 GB); the gather-fused interaction and the pooled lookup
   widen a row as they load it, the update rounds the new row to nearest even as it stores it
-  (no stochastic rounding: an update below half an fp16 ulp of the weight vanishes) and runs
-  as launches of its own; everything else of the step stays fp32.
+  (an update below half an fp16 ulp of the weight vanishes) or, with emb_rounding =
+  "stochastic", up or down at random in proportion (a device (seed, step) stream, ticked
+  behind the update), and runs as launches of its own; everything else stays fp32.
 * Learning-rate schedule on request (TrainerConfig.lr_num_warmup_steps / lr_decay_start_step /
   lr_num_decay_steps, or device_lr): the step's rates live in device memory, a one-thread
   kernel at the head of the step advances the reference's LRPolicyScheduler and every update
@@ -109,8 +110,18 @@ class TrainerConfig:
     # dlrm_s_pytorch.py:337-366).  A row is widened to fp32 as it is loaded and the updated
     # row is rounded to nearest even as it is stored; pooled embeddings, interaction,
     # gradients and dense parameters stay fp32 (DESIGN.md §18 has the limits: SGD only, no
-    # QR tables, one GPU, D % 4 == 0 and D <= 512, no stochastic rounding)
+    # QR tables, one GPU, D % 4 == 0 and D <= 512)
     emb_precision: str = "fp32"
+    # how the fp16 tables' updated row is stored: "nearest" (round to nearest even: an update
+    # below half an fp16 ulp of the weight vanishes), or "stochastic" = fbgemm's
+    # stochastic_rounding=True, its default and so the reference's run: the fp32 value is
+    # rounded up or down with the probability of its position between the two fp16
+    # neighbours, drawn from a counter-based stream of (emb_rounding_seed, step, row, column)
+    # (DESIGN.md §19).  The step count lives on the device and a one-thread kernel after the
+    # update advances it, so a captured step draws a fresh stream on every replay;
+    # DLRMTrainer.rounding_state() / set_rounding_state() read and set it for a resume
+    emb_rounding: str = "nearest"
+    emb_rounding_seed: int = 0
 
     @property
     def lr_policy_steps(self):
@@ -132,6 +143,11 @@ class TrainerConfig:
             raise ValueError(f"mlp_precision {self.mlp_precision!r}: 'fp32' or 'bf16'")
         if self.emb_precision not in ("fp32", "fp16"):
             raise ValueError(f"emb_precision {self.emb_precision!r}: 'fp32' or 'fp16'")
+        if self.emb_rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"emb_rounding {self.emb_rounding!r}: 'nearest' or 'stochastic'")
+        if self.emb_rounding == "stochastic" and self.emb_precision != "fp16":
+            raise ValueError("emb_rounding='stochastic' rounds the fp16 tables' update: it "
+                             "needs emb_precision='fp16'")
         if self.emb_precision == "fp16":
             if self.optimizer == "rwsadagrad":
                 raise NotImplementedError(
@@ -387,6 +403,10 @@ class DLRMTrainer:
             self._lr_state = ops.lr_state(
                 [self.lr, self.emb_lr, self.lr], [1.0, 1.0, 1.0 / self.world],
                 *cfg.lr_policy_steps, device=self.dev)
+        # fp16 tables rounded stochastically: the device (seed, step) of the update's stream
+        self._sr_state = None
+        if self.emb_f16 and cfg.emb_rounding == "stochastic":
+            self._sr_state = ops.sr_state(cfg.emb_rounding_seed, 0, device=self.dev)
         self.capture_mode = None  # "whole" | "segments": how the last capture() was built
         self.graphs_per_step = 0  # hipGraphs one replay of the last capture() launches
         if init:
@@ -547,6 +567,21 @@ class DLRMTrainer:
         if self._lr_state is None:
             return [float(np.float32(v)) for v in self._rates()]
         return [float(v) for v in self._lr_state.rates.cpu()]
+
+    def rounding_state(self):
+        """(seed, step) of the fp16 tables' stochastic-rounding stream: the step the NEXT
+        update draws from (0 before the first, +1 per training step, eager or replayed);
+        synchronises.  With the parameters, enough to resume a run that reproduces it."""
+        if self._sr_state is None:
+            raise RuntimeError("rounding_state: cfg.emb_rounding is not 'stochastic'")
+        return ops.sr_state_values(self._sr_state)
+
+    def set_rounding_state(self, seed: int, step: int) -> None:
+        """Set the stream's (seed, step), in place on the current stream: the next step -
+        eager, or a replay of an already captured graph - draws from it."""
+        if self._sr_state is None:
+            raise RuntimeError("set_rounding_state: cfg.emb_rounding is not 'stochastic'")
+        self._sr_state.copy_(ops.sr_state(seed, step, device=self.dev))
 
     def local_batch_size(self, B: int) -> int:
         if B % self.world:
@@ -1267,14 +1302,22 @@ class DLRMTrainer:
                     s1 = st.pop("sorted", None)
                     if s1 is not None:  # join the early sort
                         torch.cuda.current_stream(self.dev).wait_stream(s1)
-                    return fn(mode, self.weights, self.row_base, self.T_phys, B, idx, off,
-                              grad, lr=elr, eps=cfg.adagrad_eps, momentum=self.momentum,
+                    kw = dict(lr=elr, eps=cfg.adagrad_eps, momentum=self.momentum,
                               grad_batch_stride=grad.stride(0),
                               workspace=self._ws_tbe(idx.numel()),
                               max_lookups_per_table=batch.max_per_table,
                               error_flag=self.tbe_error_flag,
                               presorted=ops.PRESORTED_ANY if s1 is not None
                               else st.get("presorted", presort))
+                    if self._sr_state is not None:
+                        # the fp16 update storing sr16 of the row (never deferred: tbe_role
+                        # is off for fp16 tables), then the stream's tick behind it
+                        ops.tbe_backward(mode, self.weights, self.row_base, self.T_phys, B,
+                                         idx, off, grad, sr_state=self._sr_state, **kw)
+                        ops.sr_tick(self._sr_state)
+                        return None
+                    return fn(mode, self.weights, self.row_base, self.T_phys, B, idx, off,
+                              grad, **kw)
 
         @record_function("## Backward ##")
         def backward_single():  # one GPU: bottom backward || embedding backward

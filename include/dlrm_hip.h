@@ -129,8 +129,11 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    _backward_gather_f16 (the gather-fused dot interaction reading fp16 rows) and
  *    dlrm_tbe_backward_sgd_f16_dev (the fp16 exact-SGD update at a device-resident rate);
  *    dlrm_uniform_fill_at (a window of dlrm_uniform_fill's stream: the fp16 tables' init is
- *    staged through a bounded fp32 buffer). */
-#define DLRM_ABI_VERSION 15 /* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    staged through a bounded fp32 buffer).
+ * 16: stochastic rounding of the fp16 tables' SGD update: dlrm_tbe_backward_sgd_f16_sr (the
+ *    fp16 update storing sr16 of the fp32 value, host or device rate), the 16-byte device
+ *    dlrm_sr_state (seed, step) it reads, and dlrm_sr_tick (a one-thread step += 1). */
+#define DLRM_ABI_VERSION 16/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -996,6 +999,45 @@ int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int64_t* row_b
                                   const float* lr_dev, int64_t max_lookups_per_table,
                                   void* workspace, size_t workspace_bytes, int32_t* error_flag,
                                   int32_t presorted, dlrm_stream_t stream);
+/*
+ * ABI v16: dlrm_tbe_backward_sgd_f16 with the store rounded STOCHASTICALLY (fbgemm's
+ * stochastic_rounding=True, its default): same sort, same run order and Kahan sums, same
+ * fma(w, -lr, g) in fp32; the fp32 value v is then stored as sr16(v, r16) instead of rounded
+ * to nearest even, so an update below half an fp16 ulp of the weight survives in expectation.
+ *
+ * dlrm_sr_state: DLRM_SR_STATE_BYTES of device memory, 8-byte aligned: uint64 seed, then
+ * uint64 step.  The update reads it when its kernels run and never writes it; dlrm_sr_tick
+ * (one thread, capturable) does step += 1.  The stream is counter-based (splitmix64, uint64
+ * arithmetic that wraps), with C = ceil(D / 4) and `row` the GLOBAL row of the buffer:
+ *   key          = splitmix64(splitmix64(seed) ^ step)
+ *   word(row, d) = splitmix64(key ^ (row * C + d / 4))
+ *   r16(row, d)  = (word(row, d) >> (16 * (d % 4))) & 0xffff
+ * so a draw depends on (seed, step, row, column) alone - not on the sort path, the block
+ * length, the launch shape or the row's vector width.  Each unique row is finalised once per
+ * call: no draw is used twice.
+ *
+ * sr16(v, r16), a = |v|: NaN and +-Inf convert as the nearest-even conversion does;
+ * ulp = 2^(max(floor(log2 a), -14) - 10) (2^-24 through the subnormal range; the grid runs
+ * past 65504 to 65536, which is stored as Inf, and a >= 65536 gives Inf);
+ * t = floor(a / ulp) * ulp, frac = (a - t) / ulp; the magnitude is t + ulp if
+ * r16 < frac * 65536 and t otherwise; the result carries v's sign (a tiny negative may store
+ * -0).  A representable v is returned unchanged for every draw, and P(round away from zero)
+ * is frac.
+ *
+ * lr_dev == NULL: the host `lr` is used; else the device fp32 replaces it (as
+ * dlrm_gemm_problem.alpha_dev).  A NULL sr_state is DLRM_ERR_INVALID_ARG.
+ */
+#define DLRM_SR_STATE_BYTES 16
+int dlrm_tbe_backward_sgd_f16_sr(void* weights, int64_t D, const int64_t* row_base, int32_t T,
+                                 int32_t B, const void* indices, int32_t index_bits,
+                                 const void* offsets, int32_t offset_bits, int64_t num_lookups,
+                                 int64_t total_rows, const float* per_sample_weights,
+                                 const float* grad_out, int64_t grad_batch_stride, float lr,
+                                 const float* lr_dev, const uint64_t* sr_state,
+                                 int64_t max_lookups_per_table, void* workspace,
+                                 size_t workspace_bytes, int32_t* error_flag, int32_t presorted,
+                                 dlrm_stream_t stream);
+int dlrm_sr_tick(uint64_t* sr_state, dlrm_stream_t stream);
 int dlrm_tbe_backward_rowwise_adagrad_dev(float* weights, float* momentum, int64_t D,
                                           const int64_t* row_base, int32_t T, int32_t B,
                                           const void* indices, int32_t index_bits,

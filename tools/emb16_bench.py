@@ -8,6 +8,10 @@ measures the fp32 default and is not touched):
           over 10 batches in alternating windows (fp32, fp16, fp32, ..., --rounds of each)
           after a clock preheat: the spread between a mode's own windows is the yardstick for
           the difference between the modes.
+          --rounding: the same protocol over two fp16-table trainers instead, the update
+          stored rounded to "nearest" (the mode as it was) against "stochastic"
+          (TrainerConfig.emb_rounding: the hash and one more one-thread launch per step);
+          training step only, written to profiles/sr16_bench.json.
   trace : --steps replays of the fp16-table step and nothing else, to run under
           `rocprofv3 --kernel-trace` (tools/step_timeline.py prints one step of the trace).
   ab    : the fp32 default of this tree against a built checkout of the parent commit
@@ -15,7 +19,7 @@ measures the fp32 default and is not touched):
           fresh processes; the parent's numbers and every loss_last are written down.
 
 Writes one JSON document to --out and prints it.
-python tools/emb16_bench.py step [--config terabyte] [--steps 200] [--rounds 3]
+python tools/emb16_bench.py step [--config terabyte] [--steps 200] [--rounds 3] [--rounding]
 python tools/emb16_bench.py trace [--config terabyte] [--steps 30]
 python tools/emb16_bench.py ab --parent DIR [--steps 300] [--warmup 50] [--rounds 3]"""
 import argparse
@@ -31,10 +35,14 @@ for p in (ROOT, os.path.join(ROOT, "dlrm-yx_amd"), os.path.join(ROOT, "tools")):
 from lr_sched_bench import _stats, _time_ms, ab  # noqa: E402
 
 MODES = ("fp32", "fp16")
+ROUNDINGS = ("nearest", "stochastic")  # step --rounding: both on fp16 tables
 NB = 10  # batches a window cycles through
 
 
-def _trainer(config, dev, emb_precision):
+def _trainer(config, dev, mode):
+    kw = dict(emb_precision=mode)
+    if mode in ROUNDINGS:
+        kw = dict(emb_precision="fp16", emb_rounding=mode)
     import bench
     from dlrm_hip.trainer import DLRMTrainer, TrainerConfig
     c = bench.CONFIGS[config]
@@ -43,7 +51,7 @@ def _trainer(config, dev, emb_precision):
     cfg = TrainerConfig(m_spa=c["D"], ln_emb=c["rows"], ln_bot=c["bot"],
                         ln_top=[bench.num_int(len(c["rows"]), c["D"])] + c["top"],
                         loss_function=c["loss"], learning_rate=c["lr"], optimizer=c["optimizer"],
-                        emb_precision=emb_precision)
+                        **kw)
     return c, DLRMTrainer(cfg, device=dev, seed=1)
 
 
@@ -83,12 +91,15 @@ def step(args):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     pool = torch.cuda.graph_pool_handle()
-    runs = {m: _captured(args.config, dev, m, pool, True) for m in MODES}
-    c = runs["fp32"][0]
+    MODES = ROUNDINGS if args.rounding else globals()["MODES"]
+    base, other = MODES
+    kinds = (("train", 2),) if args.rounding else (("train", 2), ("predict", 3))
+    runs = {m: _captured(args.config, dev, m, pool, not args.rounding) for m in MODES}
+    c = runs[base][0]
     bench.preheat_device(dev, 300.0)
-    win = {kind: {m: [] for m in MODES} for kind in ("train", "predict")}
+    win = {kind: {m: [] for m in MODES} for kind, _ in kinds}
     for _ in range(args.rounds):
-        for kind, at in (("train", 2), ("predict", 3)):
+        for kind, at in kinds:
             for m in MODES:
                 win[kind][m].append(_time_ms(_cycle(runs[m][at]), args.steps, args.warmup))
     for m in MODES:
@@ -100,11 +111,13 @@ def step(args):
            "gather_fused": {m: bool(runs[m][1].gather_fused) for m in MODES}}
     for kind in win:
         row = {m: _stats(w) for m, w in win[kind].items()}
-        a, h = row["fp32"], row["fp16"]
-        row["fp16_over_fp32"] = round(h["median"] / a["median"], 4)
-        row["fp16_minus_fp32_us"] = round((h["median"] - a["median"]) * 1000.0, 2)
+        a, h = row[base], row[other]
+        row[f"{other}_over_{base}"] = round(h["median"] / a["median"], 4)
+        row[f"{other}_minus_{base}_us"] = round((h["median"] - a["median"]) * 1000.0, 2)
         row["outside_spread"] = bool(abs(h["median"] - a["median"]) > max(a["spread"], h["spread"]))
         res["ms_per_" + kind] = row
+    if args.rounding:
+        res["rounding_state"] = list(runs["stochastic"][1].rounding_state())
     return res
 
 
@@ -129,7 +142,9 @@ def main():
     s.add_argument("--steps", type=int, default=200)
     s.add_argument("--warmup", type=int, default=30)
     s.add_argument("--rounds", type=int, default=3)
-    s.add_argument("--out", default=os.path.join(ROOT, "profiles", "emb16_bench.json"))
+    s.add_argument("--rounding", action="store_true",
+                   help="fp16 tables: emb_rounding nearest against stochastic")
+    s.add_argument("--out", default=None)
     t = sub.add_parser("trace")
     t.add_argument("--config", default="terabyte")
     t.add_argument("--steps", type=int, default=30)
@@ -141,6 +156,9 @@ def main():
     a.add_argument("--rounds", type=int, default=3)
     a.add_argument("--out", default=os.path.join(ROOT, "profiles", "emb16_default_ab.json"))
     args = ap.parse_args()
+    if args.cmd == "step" and args.out is None:
+        args.out = os.path.join(ROOT, "profiles",
+                                "sr16_bench.json" if args.rounding else "emb16_bench.json")
     res = {"step": step, "trace": trace, "ab": ab}[args.cmd](args)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
