@@ -21,6 +21,18 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
+// ABI v17: the version is only reported by a library that links the entry points it names
+// (taking their addresses with the header's types fails the build if one is missing).
+static_assert(DLRM_ABI_VERSION >= 17, "abi.cpp checks the v17 entry points");
+namespace {
+[[maybe_unused]] int (*const kRowsQuantize)(const void*, int32_t, int64_t, int64_t, int32_t, void*,
+                                            int64_t, dlrm_stream_t) = &dlrm_rows_quantize;
+[[maybe_unused]] int (*const kGatherRows)(int32_t, int32_t, int32_t, const float*, int64_t,
+                                          const void*, int32_t, int64_t, const int64_t*,
+                                          const int32_t*, int32_t, float*, int64_t, int32_t*,
+                                          dlrm_stream_t) = &dlrm_interact_dot_forward_gather_rows;
+}  // namespace
+
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }
 
 extern "C" const char* dlrm_last_error(void) { return dlrm::g_last_error; }

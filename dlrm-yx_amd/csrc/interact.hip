@@ -37,12 +37,16 @@ struct GradArgs {
 // f >= 1 of sample b is row row_base[f-1] + idx[(f-1) * B + b] of W (L = 1, table-major
 // CSR indices: the lookup of apply_emb with one index per bag); feature 0 stays fa.ptr[0].
 // The kernels' GATHER template argument: 0 = pooled features, 1 = fp32 rows gathered,
-// 2 = fp16 rows gathered (dlrm_interact_dot_forward_gather_f16, gather_load4_f16 below).
+// 2 = fp16 rows gathered (dlrm_interact_dot_forward_gather_f16, gather_load4_f16 below),
+// 3 = 8-bit and 4 = 4-bit row-wise quantized rows gathered and dequantised in registers
+// (dlrm_interact_dot_forward_gather_rows, gather_load4_q below; forward kernels only).
 struct GatherArgs {
-  const float* W;           // the row buffer; [rows][D] fp16 behind the pointer when GATHER == 2
+  const float* W;           // the row buffer; [rows][D] fp16 behind the pointer when GATHER == 2,
+                            // [rows][row_bytes] packed bytes when GATHER == 3 | 4
   const int64_t* row_base;  // [F] device: table starts, row_base[F-1] = total rows
   const int32_t* idx;       // [(F-1) * B]
   int32_t* err;             // DLRM_TBE_ERR_INDEX on an index outside its table (may be null)
+  int64_t row_bytes;        // GATHER == 3 | 4: the row pitch in bytes (unused otherwise)
 };
 
 // p-th pair of the row-major lower triangle (i > j, or i >= j with self interaction).
@@ -254,6 +258,44 @@ __device__ __forceinline__ float4 gather_load4_f16(const GatherArgs& gt, const f
   return v;
 }
 
+// Quantized tables (GATHER == 3: DLRM_ROWS_Q8, 4: DLRM_ROWS_Q4): a lane reads the levels of
+// its four columns as one 4-byte (Q8) or 2-byte (Q4) load and the row's scale and bias as one
+// 8-byte (Q8: two fp32) or 4-byte (Q4: two fp16) load, the same address in every lane of the
+// row, and forms fmaf(scale, q, bias) per column in registers: what tbe_rows_fwd_kernel gives
+// a one-index bag.  The LDS image and everything after it are the fp32 kernel's.  `tab`: the
+// lane holds a table row (1 <= f < F, index in range); other lanes read valid bytes of x for
+// both loads (callers zero or mask them).  x as in gather_load4_f16: loaded by every lane of
+// the first row group and selected, so no load sits in a branch.
+template <int D, int GATHER>
+__device__ __forceinline__ float4 gather_load4_q(const GatherArgs& gt, const float* xrow, bool isx,
+                                                 bool tab, int64_t g, int col, bool first) {
+  const uint8_t* xb = reinterpret_cast<const uint8_t*>(xrow);
+  const uint8_t* row = reinterpret_cast<const uint8_t*>(gt.W) + (tab ? g : 0) * gt.row_bytes;
+  float4 q;
+  float scale, bias;
+  if constexpr (GATHER == 3) {
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(tab ? row + col : xb + col);
+    const float2 sb = *reinterpret_cast<const float2*>(tab ? row + D : xb);
+    q = make_float4((float)(u & 0xff), (float)((u >> 8) & 0xff), (float)((u >> 16) & 0xff),
+                    (float)(u >> 24));
+    scale = sb.x, bias = sb.y;
+  } else {
+    const uint32_t u = *reinterpret_cast<const uint16_t*>(tab ? row + col / 2 : xb + col / 2);
+    const uint32_t sb = *reinterpret_cast<const uint32_t*>(tab ? row + D / 2 : xb);
+    q = make_float4((float)(u & 0xf), (float)((u >> 4) & 0xf), (float)((u >> 8) & 0xf),
+                    (float)((u >> 12) & 0xf));
+    scale = (float)__builtin_bit_cast(_Float16, (unsigned short)(sb & 0xffff));
+    bias = (float)__builtin_bit_cast(_Float16, (unsigned short)(sb >> 16));
+  }
+  float4 v = make_float4(fmaf(scale, q.x, bias), fmaf(scale, q.y, bias), fmaf(scale, q.z, bias),
+                         fmaf(scale, q.w, bias));
+  if (first) {
+    const float4 xv = *reinterpret_cast<const float4*>(xrow + col);
+    if (isx) v = xv;
+  }
+  return v;
+}
+
 template <int D>
 __device__ __forceinline__ float* grad_row_ptr(const GradArgs& ga, int F, int64_t b, int i0,
                                                int sub) {
@@ -305,7 +347,13 @@ __global__ __launch_bounds__(256) void interact_dot_fwd_v4(int B, int F, FeatArg
       float4 v[NI];
 #pragma unroll
       for (int q = 0; q < NI; ++q) {
-        if constexpr (GATHER == 2) {
+        if constexpr (GATHER >= 3) {
+          const int f = q * RPI + sub;
+          const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
+          v[q] = gather_load4_q<D, GATHER>(gt, fa.ptr[0] + bl * fa.bs[0], f == 0,
+                                           f >= 1 && f < F && g >= 0, g, 4 * c, q == 0);
+          if (f >= 1 && g < 0) v[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (GATHER == 2) {
           const int f = q * RPI + sub;
           const int64_t g = __shfl(grow, f < 64 ? f : 0, 64);
           v[q] = gather_load4_f16<D>(gt, fa.ptr[0] + bl * fa.bs[0], f, g, 4 * c, q == 0);
@@ -737,13 +785,15 @@ __device__ __forceinline__ void v5_load_t(int B, int F, const FeatArgs& fa, cons
         const int64_t r = gt.idx[(int64_t)(f - 1) * B + b];
         if (r >= 0 && r < n) {
           g = lo + r;
-          if constexpr (GATHER != 2) src = gt.W + g * D;
+          if constexpr (GATHER == 1) src = gt.W + g * D;
         } else {
           zero = true;
           if (flag && c == 0 && gt.err) atomicOr(gt.err, DLRM_TBE_ERR_INDEX);
         }
       }
-      if constexpr (GATHER == 2)
+      if constexpr (GATHER >= 3)
+        v[q] = gather_load4_q<D, GATHER>(gt, src, f == 0, g >= 0, g, 4 * c, q == 0);
+      else if constexpr (GATHER == 2)
         v[q] = gather_load4_f16<D>(gt, src, f, g, 4 * c, q == 0);
       else
         v[q] = *reinterpret_cast<const float4*>(src + 4 * c);
@@ -1184,13 +1234,15 @@ extern "C" int dlrm_interact_cat_backward(int32_t B, int32_t F, int32_t D,
 // One-hot lookup fused into the interaction (one GPU, L = 1): features 1..F-1 are gathered
 // straight from the table buffer (no [B, T, D] pooled-embedding round trip through HBM).
 // Same math and output as dlrm_interact_dot_forward on the looked-up rows.
-// G = 1: fp32 rows; G = 2: fp16 rows (one 8-byte read per lane, widened in registers).
+// G = 1: fp32 rows; G = 2: fp16 rows (one 8-byte read per lane, widened in registers);
+// G = 3 | 4: Q8 | Q4 rows of row_bytes bytes (levels, scale and bias read, dequantised in
+// registers).
 namespace {
 template <int G>
 int forward_gather(const char* name, int32_t B, int32_t F, int32_t D, const float* x,
                    int64_t x_bstride, const float* weights, const int64_t* row_base,
                    const int32_t* indices, int32_t self_interaction, float* out, int64_t ld_out,
-                   int32_t* error_flag, dlrm_stream_t stream) {
+                   int32_t* error_flag, dlrm_stream_t stream, int64_t row_bytes = 0) {
   DLRM_ARG(B >= 0 && F >= 2 && F <= 32, "%s: need F in [2,32]", name);
   DLRM_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, DLRM_ERR_UNSUPPORTED,
                "%s: D must be 16, 32, 64 or 128", name);
@@ -1204,7 +1256,7 @@ int forward_gather(const char* name, int32_t B, int32_t F, int32_t D, const floa
   DLRM_ARG(ld_out >= D + npairs, "%s: ld_out < D + pairs", name);
   FeatArgs fa{};
   for (int f = 0; f < F; ++f) fa.ptr[f] = x, fa.bs[f] = x_bstride;
-  const GatherArgs gt{weights, row_base, indices, error_flag};
+  const GatherArgs gt{weights, row_base, indices, error_flag, row_bytes};
   const int width = D + npairs;
   hipStream_t st = dlrm::as_stream(stream);
   if (fwd_version(D, B) == 5) {
@@ -1251,6 +1303,33 @@ extern "C" int dlrm_interact_dot_forward_gather_f16(int32_t B, int32_t F, int32_
   return forward_gather<2>("dlrm_interact_dot_forward_gather_f16", B, F, D, x, x_bstride,
                            static_cast<const float*>(weights), row_base, indices,
                            self_interaction, out, ld_out, error_flag, stream);
+}
+
+// The same on row-wise quantized tables (ABI v17, forward only: inference).  Each level is
+// dequantised as fmaf(scale, q, bias), the value dlrm_tbe_forward_rows gives a one-index bag,
+// so the result is bitwise the fp32 entry point's on the dequantised table.
+extern "C" int dlrm_interact_dot_forward_gather_rows(int32_t B, int32_t F, int32_t D,
+                                                     const float* x, int64_t x_bstride,
+                                                     const void* weights, int32_t format,
+                                                     int64_t row_bytes, const int64_t* row_base,
+                                                     const int32_t* indices,
+                                                     int32_t self_interaction, float* out,
+                                                     int64_t ld_out, int32_t* error_flag,
+                                                     dlrm_stream_t stream) {
+  const char* name = "dlrm_interact_dot_forward_gather_rows";
+  DLRM_REQUIRE(format == DLRM_ROWS_Q8 || format == DLRM_ROWS_Q4, DLRM_ERR_UNSUPPORTED,
+               "%s: format %d is not Q8 | Q4 (fp32 and fp16 rows have entry points of their own)",
+               name, format);
+  DLRM_REQUIRE(D == 16 || D == 32 || D == 64 || D == 128, DLRM_ERR_UNSUPPORTED,
+               "%s: D must be 16, 32, 64 or 128", name);
+  DLRM_ARG(row_bytes == dlrm_tbe_row_bytes(format, D), "%s: row_bytes %lld != %lld", name,
+           (long long)row_bytes, (long long)dlrm_tbe_row_bytes(format, D));
+  const float* w = static_cast<const float*>(weights);
+  if (format == DLRM_ROWS_Q8)
+    return forward_gather<3>(name, B, F, D, x, x_bstride, w, row_base, indices, self_interaction,
+                             out, ld_out, error_flag, stream, row_bytes);
+  return forward_gather<4>(name, B, F, D, x, x_bstride, w, row_base, indices, self_interaction,
+                           out, ld_out, error_flag, stream, row_bytes);
 }
 
 // Its backward: T re-gathered from the same (not yet updated) rows; gradients as

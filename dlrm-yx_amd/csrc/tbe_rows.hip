@@ -15,6 +15,9 @@
 // lanes per (table, bag), every lane owning 4 consecutive elements per 4*LPB, four rows of
 // a bag in flight.  HBM-bound: a C3 row is 512 B in fp32, 256 B in fp16, 136 B in Q8 and
 // 68 B in Q4, so the gather moves 2x / 3.8x / 7.5x fewer bytes.
+//
+// dlrm_rows_quantize (below the lookup) produces the Q8 / Q4 rows on the device from fp32 or
+// fp16 rows, bitwise torch's packers.
 #include "common.hpp"
 
 namespace {
@@ -218,7 +221,185 @@ int rows_dispatch(const uint8_t* W, int64_t row_bytes, int64_t D, const int64_t*
                                                 out, out_bs, err, st);
 }
 
+// ------------------------------------------------------- row-wise quantizer --
+// dlrm_rows_quantize: fp32 / fp16 rows -> Q8 / Q4 rows, bitwise what torch.ops.quantized
+// .embedding_bag_byte_prepack / embedding_bag_4bit_prepack return for the same fp32 rows
+// (DLRM_Net.quantize_embedding, dlrm_s_pytorch.py:609-625), on the device.  The lookup's lane
+// groups: LPB lanes per row, each lane owning the columns [4 chunk, 4 chunk + 4) of chunk =
+// gl (+ LPB above D = 256), 64 / LPB rows per wave.  A lane loads its columns once
+// (nontemporal: the table is read once), the row's min and max meet by a butterfly inside
+// the group (order-independent, so exact), every lane quantises and stores its own columns
+// and the group's first lane stores scale and bias.  All arithmetic is fp32 with one
+// rounding per operation (true division, rintf, no contraction).
+typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_nt __attribute__((ext_vector_type(2)));
+
+template <int SRC>
+__device__ __forceinline__ float4 quant_load4(const void* __restrict__ src, int64_t elem) {
+  if constexpr (SRC == DLRM_ROWS_F32) {
+    const f32x4_nt v = __builtin_nontemporal_load(
+        reinterpret_cast<const f32x4_nt*>(static_cast<const float*>(src) + elem));
+    return make_float4(v.x, v.y, v.z, v.w);
+  } else {  // fp16 rows, widened exactly
+    const u32x2_nt u = __builtin_nontemporal_load(
+        reinterpret_cast<const u32x2_nt*>(static_cast<const uint16_t*>(src) + elem));
+    return make_float4(half_bits_to_float(u.x & 0xffff), half_bits_to_float(u.x >> 16),
+                       half_bits_to_float(u.y & 0xffff), half_bits_to_float(u.y >> 16));
+  }
+}
+
+__device__ __forceinline__ float half_rne(float x) { return (float)(_Float16)x; }
+__device__ __forceinline__ uint16_t half_bits(float x) {
+  return __builtin_bit_cast(unsigned short, (_Float16)x);
+}
+
+__device__ __forceinline__ uint32_t quant_level(float x, float mn, float inv, float top) {
+#pragma clang fp contract(off)
+  const float d = x - mn;
+  float q = rintf(d * inv);  // ties to even
+  q = q < 0.f ? 0.f : (q > top ? top : q);
+  return (uint32_t)q;
+}
+
+template <int SRC, int FMT, int LPB, int MAXV>
+__global__ __launch_bounds__(256) void rows_quantize_kernel(const void* __restrict__ src,
+                                                            int64_t rows, int D,
+                                                            uint8_t* __restrict__ dst) {
+#pragma clang fp contract(off)
+  constexpr int GPW = kWave / LPB;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int g = lane / LPB;
+  const int gl = lane - g * LPB;
+  const int nchunks = D / 4;
+  const int64_t row_bytes = FMT == DLRM_ROWS_Q8 ? D + 8 : D / 2 + 4;
+  const int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x / kWave);
+  for (int64_t r0 = wave_id * GPW; r0 < rows; r0 += nwaves * GPW) {  // wave-uniform trip count
+    const int64_t r = r0 + g;
+    float4 v[MAXV];
+    bool ok[MAXV];
+    float mn = __builtin_inff(), mx = -__builtin_inff();
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int chunk = gl + c * LPB;
+      ok[c] = r < rows && chunk < nchunks;
+      v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ok[c]) {
+        v[c] = quant_load4<SRC>(src, r * D + 4 * chunk);
+        mn = fminf(fminf(mn, fminf(v[c].x, v[c].y)), fminf(v[c].z, v[c].w));
+        mx = fmaxf(fmaxf(mx, fmaxf(v[c].x, v[c].y)), fmaxf(v[c].z, v[c].w));
+      }
+    }
+#pragma unroll
+    for (int o = LPB / 2; o >= 1; o >>= 1) {  // stays inside the aligned group of LPB lanes
+      mn = fminf(mn, __shfl_xor(mn, o, kWave));
+      mx = fmaxf(mx, __shfl_xor(mx, o, kWave));
+    }
+    uint8_t* row = dst + r * row_bytes;
+    if constexpr (FMT == DLRM_ROWS_Q8) {
+      const float range = mx - mn;
+      const float scale = range / 255.0f;
+      const float inv = 255.0f / (range + 1e-8f);
+#pragma unroll
+      for (int c = 0; c < MAXV; ++c) {
+        if (ok[c]) {
+          const uint32_t u = quant_level(v[c].x, mn, inv, 255.f) |
+                             (quant_level(v[c].y, mn, inv, 255.f) << 8) |
+                             (quant_level(v[c].z, mn, inv, 255.f) << 16) |
+                             (quant_level(v[c].w, mn, inv, 255.f) << 24);
+          *reinterpret_cast<uint32_t*>(row + 4 * (gl + c * LPB)) = u;
+        }
+      }
+      if (gl == 0 && r < rows) {
+        float* sb = reinterpret_cast<float*>(row + D);
+        sb[0] = scale;
+        sb[1] = mn;
+      }
+    } else {
+      const float mnh = half_rne(mn);
+      const float range = mx - mnh;
+      float scale = half_rne(range / 15.0f);
+      if (scale == 0.f) scale = 1.f;
+      float inv = 1.0f / scale;
+      if (__builtin_isinf(inv)) scale = inv = 1.f;
+#pragma unroll
+      for (int c = 0; c < MAXV; ++c) {
+        if (ok[c]) {
+          const uint32_t u = quant_level(v[c].x, mnh, inv, 15.f) |
+                             (quant_level(v[c].y, mnh, inv, 15.f) << 4) |
+                             (quant_level(v[c].z, mnh, inv, 15.f) << 8) |
+                             (quant_level(v[c].w, mnh, inv, 15.f) << 12);
+          *reinterpret_cast<uint16_t*>(row + 2 * (gl + c * LPB)) = (uint16_t)u;
+        }
+      }
+      if (gl == 0 && r < rows) {  // Q4 rows are 2-byte aligned in general
+        uint16_t* sb = reinterpret_cast<uint16_t*>(row + D / 2);
+        sb[0] = half_bits(scale);
+        sb[1] = half_bits(mnh);
+      }
+    }
+  }
+}
+
+template <int SRC, int FMT>
+int launch_rows_quantize(const void* src, int64_t rows, int D, uint8_t* dst, hipStream_t st) {
+  const int nchunks = D / 4;
+  int lpb = 1;
+  while (lpb < nchunks && lpb < 64) lpb <<= 1;
+  const int gpw = 64 / lpb;
+  int64_t blocks = dlrm::ceil_div(dlrm::ceil_div(rows, (int64_t)gpw), 4);
+  if (blocks > 8192) blocks = 8192;
+#define RQ(LPB, MV)                                                                           \
+  hipLaunchKernelGGL((rows_quantize_kernel<SRC, FMT, LPB, MV>), dim3(blocks), dim3(256), 0, st, \
+                     src, rows, D, dst)
+  switch (lpb) {
+    case 1: RQ(1, 1); break;
+    case 2: RQ(2, 1); break;
+    case 4: RQ(4, 1); break;
+    case 8: RQ(8, 1); break;
+    case 16: RQ(16, 1); break;
+    case 32: RQ(32, 1); break;
+    default:
+      if (nchunks <= 64)
+        RQ(64, 1);
+      else
+        RQ(64, 2);
+  }
+#undef RQ
+  DLRM_LAUNCH_CHECK("dlrm_rows_quantize");
+  return DLRM_OK;
+}
+
 }  // namespace
+
+extern "C" int dlrm_rows_quantize(const void* src, int32_t src_format, int64_t rows, int64_t D,
+                                  int32_t dst_format, void* dst, int64_t dst_row_bytes,
+                                  dlrm_stream_t stream) {
+  const char* name = "dlrm_rows_quantize";
+  DLRM_ARG(src_format == DLRM_ROWS_F32 || src_format == DLRM_ROWS_F16,
+           "%s: source format %d is not F32 | F16", name, src_format);
+  DLRM_ARG(dst_format == DLRM_ROWS_Q8 || dst_format == DLRM_ROWS_Q4,
+           "%s: destination format %d is not Q8 | Q4", name, dst_format);
+  DLRM_ARG(rows >= 0 && D > 0, "%s: bad sizes", name);
+  DLRM_REQUIRE(D % 4 == 0 && D <= 512, DLRM_ERR_UNSUPPORTED,
+               "%s: D must be a multiple of 4 and <= 512 (D=%lld)", name, (long long)D);
+  DLRM_ARG(dst_row_bytes == min_row_bytes(dst_format, D), "%s: dst_row_bytes %lld != %lld", name,
+           (long long)dst_row_bytes, (long long)min_row_bytes(dst_format, D));
+  if (rows == 0) return DLRM_OK;
+  DLRM_ARG(src && dst, "%s: null pointer", name);
+  DLRM_REQUIRE((reinterpret_cast<uintptr_t>(src) % (src_format == DLRM_ROWS_F32 ? 16 : 8)) == 0 &&
+                   (reinterpret_cast<uintptr_t>(dst) % (dst_format == DLRM_ROWS_Q8 ? 4 : 2)) == 0,
+               DLRM_ERR_UNSUPPORTED, "%s: misaligned source or destination", name);
+  hipStream_t st = dlrm::as_stream(stream);
+  uint8_t* out = static_cast<uint8_t*>(dst);
+  if (src_format == DLRM_ROWS_F32)
+    return dst_format == DLRM_ROWS_Q8
+               ? launch_rows_quantize<DLRM_ROWS_F32, DLRM_ROWS_Q8>(src, rows, (int)D, out, st)
+               : launch_rows_quantize<DLRM_ROWS_F32, DLRM_ROWS_Q4>(src, rows, (int)D, out, st);
+  return dst_format == DLRM_ROWS_Q8
+             ? launch_rows_quantize<DLRM_ROWS_F16, DLRM_ROWS_Q8>(src, rows, (int)D, out, st)
+             : launch_rows_quantize<DLRM_ROWS_F16, DLRM_ROWS_Q4>(src, rows, (int)D, out, st);
+}
 
 extern "C" int64_t dlrm_tbe_row_bytes(int32_t format, int64_t D) { return min_row_bytes(format, D); }
 

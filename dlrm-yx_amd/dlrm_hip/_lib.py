@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 16
+ABI_VERSION = 17
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -213,6 +213,12 @@ SIGNATURES = {
                                                c_int32, c_int64, c_int64, P, P, c_int64, c_float,
                                                P, P, c_int64, P, c_size_t, P, c_int32, P]),
     "dlrm_sr_tick": (c_int32, [P, P]),
+    # ABI v17: int8 / int4 embedding tables for inference (the device row-wise quantizer; the
+    # gather-fused interaction forward on Q8 / Q4 rows)
+    "dlrm_rows_quantize": (c_int32, [P, c_int32, c_int64, c_int64, c_int32, P, c_int64, P]),
+    "dlrm_interact_dot_forward_gather_rows": (c_int32, [c_int32, c_int32, c_int32, P, c_int64, P,
+                                                        c_int32, c_int64, P, P, c_int32, P,
+                                                        c_int64, P, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

@@ -331,6 +331,38 @@ def tbe_forward_rows(weights: torch.Tensor, fmt: int, D: int, row_base: torch.Te
     return out
 
 
+def quant_format(bits: int) -> int:
+    """ROWS_Q8 | ROWS_Q4 for a width of 8 | 4 bits (ValueError otherwise)."""
+    if bits not in (4, 8):
+        raise ValueError(f"row-wise quantized rows are 8 or 4 bits wide, not {bits!r}")
+    return ROWS_Q4 if bits == 4 else ROWS_Q8
+
+
+def rows_quantize(src: torch.Tensor, bits: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dlrm_rows_quantize: [rows, D] fp32 or fp16 rows packed row-wise to ``bits`` (8 | 4) on
+    the device, bitwise torch.ops.quantized.embedding_bag_byte_prepack /
+    embedding_bag_4bit_prepack of the same rows as fp32.  Returns uint8 [rows, row_bytes]
+    (``out``: such a contiguous tensor to fill), the layout tbe_forward_rows and
+    interact_forward_gather_rows read."""
+    fmt = quant_format(bits)
+    if src.dtype not in (torch.float32, torch.float16) or src.dim() != 2 \
+            or not src.is_contiguous():
+        raise ValueError("rows_quantize: contiguous [rows, D] fp32 or fp16 rows, not "
+                         f"{src.dtype} {tuple(src.shape)}")
+    _check_cuda(src, out)
+    rows, D = src.shape
+    row_bytes = tbe_row_bytes(fmt, D)
+    if out is None:
+        out = torch.empty((rows, row_bytes), dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (rows, row_bytes) \
+            or not out.is_contiguous():
+        raise ValueError(f"rows_quantize: out must be contiguous uint8 [{rows}, {row_bytes}]")
+    _lib.call("dlrm_rows_quantize", _p(src), ROWS_F32 if src.dtype == torch.float32 else ROWS_F16,
+              rows, D, fmt, _p(out), row_bytes, _stream(src.device))
+    return out
+
+
 def tbe_backward_workspace_size(num_lookups: int, total_rows: int, D: int) -> int:
     return _lib.query("dlrm_tbe_backward_workspace_size", num_lookups, total_rows, D)
 
@@ -653,6 +685,35 @@ def interact_forward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: to
     _lib.call(entry, B, F, D, _p(x), x.stride(0), _p(weights),
               _p(row_base), _p(indices), int(self_interaction), _p(out), out.stride(0),
               _p(error_flag), _stream(x.device))
+    return out
+
+
+def interact_forward_gather_rows(x: torch.Tensor, packed: torch.Tensor, fmt: int, D: int,
+                                 row_base: torch.Tensor, indices: torch.Tensor,
+                                 self_interaction: bool = False,
+                                 out: Optional[torch.Tensor] = None,
+                                 error_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """interact_forward_gather on row-wise quantized tables (forward only):
+    ``packed`` is uint8 [rows, row_bytes] in ``fmt`` ROWS_Q8 | ROWS_Q4 (rows_quantize's output),
+    each level dequantised as fma(scale, q, bias) in registers.  Bitwise
+    interact_forward_gather on the dequantised fp32 table
+    (dlrm_interact_dot_forward_gather_rows)."""
+    _check_cuda(x, packed, row_base, indices)
+    if packed.dtype != torch.uint8 or packed.dim() != 2:
+        raise ValueError(f"gather interaction on packed rows: uint8 [rows, row_bytes], not "
+                         f"{packed.dtype}")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D:
+        raise ValueError(f"gather interaction on packed rows: x is fp32 [B, {D}]")
+    B = x.shape[0]
+    F = row_base.numel()
+    npairs = F * (F + 1) // 2 if self_interaction else F * (F - 1) // 2
+    if indices.dtype != torch.int32 or indices.numel() != (F - 1) * B:
+        raise ValueError("gather interaction: int32 indices [(F-1) * B] (one per bag)")
+    if out is None:
+        out = torch.empty(B, D + npairs, dtype=torch.float32, device=x.device)
+    _lib.call("dlrm_interact_dot_forward_gather_rows", B, F, D, _p(x), x.stride(0), _p(packed),
+              int(fmt), packed.stride(0), _p(row_base), _p(indices), int(self_interaction),
+              _p(out), out.stride(0), _p(error_flag), _stream(x.device))
     return out
 
 

@@ -34,6 +34,10 @@ optimizer update.  Layout decisions (MI355X-first):
   kernel at the head of the step advances the reference's LRPolicyScheduler and every update
   kernel reads its rate when it runs, so a captured step walks the schedule on replay.  With
   the defaults the rates are host floats and the step is unchanged.
+* int8 / int4 tables for inference on request (quantize_embedding(bits), then emb_bits=bits on
+  predict / capture_predict / evaluate; one GPU, plain tables): a row-wise quantized snapshot
+  of the tables packed on the device (C3: 7.4 / 3.7 GB), read by the gather-fused interaction
+  or the pooled Q8 / Q4 lookup; the masters stay and the training step never reads it.
 """
 from __future__ import annotations
 
@@ -277,6 +281,9 @@ class DLRMTrainer:
         self.weights = torch.empty((max(self.total_rows, 1), D),
                                    dtype=torch.float16 if self.emb_f16 else torch.float32,
                                    device=self.dev)
+        # row-wise quantized snapshots of the tables for predict(emb_bits=8 | 4), one buffer per
+        # width, filled by quantize_embedding; the training step never reads them
+        self._qrows = {}
         self.momentum = None
         if cfg.optimizer == "rwsadagrad":
             self.momentum = torch.zeros(max(self.total_rows, 1), dtype=torch.float32,
@@ -832,7 +839,7 @@ class DLRMTrainer:
         layer and pass.  Every other piece is the same code for both."""
         cfg = self.cfg
         train = predict is None
-        metrics, precision = (None, cfg.mlp_precision) if train else predict
+        metrics, precision, emb_bits = (None, cfg.mlp_precision, 32) if train else predict
         fp32 = precision == "fp32"
         D = self.D
         Bl = batch.X.shape[0]
@@ -859,6 +866,11 @@ class DLRMTrainer:
         # and the update MODE_SGD_F16 as launches of its own (no fp16 launch role: tbe_role
         # below is off for them)
         f16 = self.emb_f16
+        # quantized tables (predict's emb_bits = 8 | 4, forward only): a switch beside f16 - the
+        # gather-fused interaction reads the packed snapshot, the pooled lookup is
+        # dlrm_tbe_forward_rows on it; the master tables are not read at all
+        qrows = None if emb_bits == 32 else self.quantized_rows(emb_bits)
+        qfmt = None if qrows is None else ops.quant_format(emb_bits)
         # The 16-bit step has no launch role, no bottom chain in the lookup launch and no
         # side-stream overlap (DESIGN.md §16 has the plan to give it them): they are switched
         # off here, once, and the pieces below take the branches they take in an fp32 step
@@ -933,7 +945,11 @@ class DLRMTrainer:
                     st["csr"] = self._phys_csr(batch, B)
                 idx, off = st["csr"]
                 out = bufs["P"] if self.qr_active else bufs["E"]
-                if f16 and not gather:
+                if qrows is not None:  # forward only, never with QR: one pooled Q lookup
+                    ops.tbe_forward_rows(qrows, qfmt, D, self.row_base, self.T_phys, B, idx,
+                                         off, out=out, out_batch_stride=out.stride(0),
+                                         error_flag=self.tbe_error_flag)
+                elif f16 and not gather:
                     # the pooled lookup on fp16 rows is a launch of its own; the lookup launch
                     # keeps its sort role (the sort never reads a row) and the bottom MLP's
                     # where the per-table sort applies, else the backward sorts itself
@@ -998,7 +1014,11 @@ class DLRMTrainer:
         def interaction_fwd():
             x, feats = self._features(bufs, Bl)
             with record_function("module::forward_pass::interaction"), prof("interaction_fwd"):
-                if gather:  # one-hot lookup fused: rows read straight from the tables
+                if gather and qrows is not None:  # the same on the packed snapshot
+                    ops.interact_forward_gather_rows(x, qrows, qfmt, D, self.row_base,
+                                                     batch.indices, cfg.arch_interaction_itself,
+                                                     out=bufs["R"], error_flag=self.tbe_error_flag)
+                elif gather:  # one-hot lookup fused: rows read straight from the tables
                     ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
                                                 cfg.arch_interaction_itself, out=bufs["R"],
                                                 error_flag=self.tbe_error_flag)
@@ -1614,14 +1634,66 @@ class DLRMTrainer:
         return run, "segments", graphs[0]
 
     # ---------------------------------------------------------- evaluation --
-    def predict(self, batch: Batch, metrics=None, precision: str = "fp32") -> torch.Tensor:
+    def _quant_refusals(self) -> None:
+        if self.qr:
+            raise NotImplementedError(
+                "quantized embedding tables with qr_flag: the QR combine runs on fp32 tables "
+                "only (DESIGN.md §20)")
+        if self.distributed:
+            raise NotImplementedError(
+                "quantized embedding tables on the multi-GPU schedule: they run on one GPU "
+                "only (DESIGN.md §20)")
+        if self.D % 4 or self.D > 512:
+            raise NotImplementedError(
+                f"quantized embedding tables with m_spa={self.D}: the packed rows take D a "
+                "multiple of 4 and at most 512 (dlrm_rows_quantize; DESIGN.md §20)")
+
+    def quantize_embedding(self, bits: int) -> torch.Tensor:
+        """Pack the engine's current tables (fp32, or emb_precision "fp16") row-wise to
+        ``bits`` (8 | 4) on the device: one dlrm_rows_quantize over the whole row buffer into
+        an engine-owned uint8 [rows, row_bytes] buffer that predict(..., emb_bits=bits) reads
+        (the reference's --quantize-emb-with-bit, DLRM_Net.quantize_embedding,
+        dlrm_s_pytorch.py:609-625; bitwise torch's CPU packers).  Row pitches are uniform, so
+        ``row_base`` serves both buffers.
+
+        There is one buffer per width and a second call re-packs into the same storage, so
+        an already captured predict graph reads the new values.  The packed rows are a
+        SNAPSHOT: the master tables stay, training is untouched, and training after this
+        call does not move the packed rows until the next call."""
+        ops.quant_format(bits)
+        self._quant_refusals()
+        self._qrows[bits] = ops.rows_quantize(self.weights, bits, out=self._qrows.get(bits))
+        return self._qrows[bits]
+
+    def quantized_rows(self, bits: int) -> torch.Tensor:
+        """The packed buffer of ``bits`` (uint8 [rows, row_bytes], table t = rows
+        [row_base[t], row_base[t+1]))."""
+        ops.quant_format(bits)
+        if bits not in self._qrows:
+            raise RuntimeError(f"no {bits}-bit tables: call quantize_embedding({bits}) first")
+        return self._qrows[bits]
+
+    def _emb_bits(self, emb_bits: int) -> int:
+        """Validate predict's ``emb_bits``: 32 = the master tables, 8 | 4 = the packed
+        snapshot of that width (which must exist)."""
+        if emb_bits == 32:
+            return 32
+        if emb_bits not in (4, 8):
+            raise ValueError(f"emb_bits {emb_bits!r}: 32, 8 or 4")
+        self._quant_refusals()
+        self.quantized_rows(emb_bits)
+        return int(emb_bits)
+
+    def predict(self, batch: Batch, metrics=None, precision: str = "fp32",
+                emb_bits: int = 32) -> torch.Tensor:
         """Forward only: prob [B_local] for ``batch`` (a device tensor owned by this batch
         size, overwritten by the next predict of it).  Writes no weight, no optimizer
         state, no gradient and no pending launch role; with ``metrics`` (a
         metrics.EvalState) the head also logs every (prob, batch.target) sample.
         ``precision`` "bf16" | "fp16": the MLP layers below the head on the 16-bit MFMA
-        (predict_segments)."""
-        for _kind, fn in self.predict_segments(batch, metrics, precision):
+        (predict_segments).  ``emb_bits`` 8 | 4: the embedding rows from the packed snapshot
+        of quantize_embedding(emb_bits) instead of the master tables."""
+        for _kind, fn in self.predict_segments(batch, metrics, precision, emb_bits):
             fn()
         return self._predict_bufs(self._buffers(batch.X.shape[0],
                                                 batch.X.shape[0] * self.world))["prob"]
@@ -1639,7 +1711,8 @@ class DLRMTrainer:
                 "ws_side": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev)}
         return pb
 
-    def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32"):
+    def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32",
+                         emb_bits: int = 32):
         """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
         ``segments()`` and built from the same pieces (_build): the lookup
         (dlrm_tbe_forward; nothing of the backward's sort), the bottom MLP (one GPU: beside
@@ -1654,37 +1727,51 @@ class DLRMTrainer:
         fp32 accumulate, fp32 bias and ReLU, fp32 activations; the fused bottom chain is not
         used.  The lookup, the interaction, the all-to-all and the head (its K -> 1 layer
         stays fp32) are the fp32 path's.  Only out[:, :N] of an activation buffer is
-        written, so the constant-1 columns the training step relies on stay."""
-        return self._build(batch, predict=(metrics, _precision(precision)))
+        written, so the constant-1 columns the training step relies on stay.
 
-    def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32"):
+        ``emb_bits`` 8 | 4 (the reference's --quantize-emb-with-bit): the rows come from the
+        packed snapshot quantize_embedding built (RuntimeError without one) - the
+        gather-fused interaction dequantises them in registers
+        (dlrm_interact_dot_forward_gather_rows, still no lookup launch), otherwise the pooled
+        lookup is one dlrm_tbe_forward_rows.  It composes with every ``precision`` and with
+        ``metrics``; 32 is the path above, bit for bit."""
+        return self._build(batch, predict=(metrics, _precision(precision),
+                                           self._emb_bits(emb_bits)))
+
+    def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32",
+                        emb_bits: int = 32):
         """A replayable forward-only pass for ``batch`` (capture()'s modes over
         predict_segments).  Run one eager predict of this batch size first (allocations).
         Each call of the returned callable scores the batch's current contents into the
         tensor predict() returns; with ``metrics`` every call appends B_local samples (the
-        log's cursor lives on the device).  ``precision``: as predict_segments."""
+        log's cursor lives on the device).  ``precision``, ``emb_bits``: as predict_segments
+        (the graph holds the packed buffer's address; quantize_embedding re-packs in place)."""
         _precision(precision)
+        self._emb_bits(emb_bits)
         run, _mode, _graphs = self._capture_segments(
-            lambda: self.predict_segments(batch, metrics, precision), pool, None)
+            lambda: self.predict_segments(batch, metrics, precision, emb_bits), pool, None)
         return run
 
-    def evaluate(self, batches, metrics, precision: str = "fp32") -> dict:
+    def evaluate(self, batches, metrics, precision: str = "fp32", emb_bits: int = 32) -> dict:
         """Score every batch into ``metrics`` (a metrics.EvalState, not reset here) and
         return its compute() dict (on several ranks: over all ranks' samples).  One graph
         per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
         batches are copied into.  Index errors are checked once, at the end.
-        ``precision``: as predict_segments (part of the graph key)."""
+        ``precision``, ``emb_bits``: as predict_segments (parts of the graph key)."""
         _precision(precision)
+        self._emb_bits(emb_bits)
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
-                   self._gather_applies(batch), precision)
+                   self._gather_applies(batch), precision, emb_bits)
             if key not in graphs:
                 fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
                               batch.target.clone(), batch.max_per_table, batch.one_hot)
-                self.predict(fixed, precision=precision)  # eager, unlogged: allocations
+                self.predict(fixed, precision=precision,
+                             emb_bits=emb_bits)  # eager, unlogged: allocations
                 torch.cuda.current_stream(self.dev).synchronize()
-                graphs[key] = (fixed, self.capture_predict(fixed, metrics, precision=precision))
+                graphs[key] = (fixed, self.capture_predict(fixed, metrics, precision=precision,
+                                                           emb_bits=emb_bits))
             fixed, run = graphs[key]
             fixed.X.copy_(batch.X)
             fixed.offsets.copy_(batch.offsets)

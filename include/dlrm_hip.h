@@ -132,8 +132,12 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    staged through a bounded fp32 buffer).
  * 16: stochastic rounding of the fp16 tables' SGD update: dlrm_tbe_backward_sgd_f16_sr (the
  *    fp16 update storing sr16 of the fp32 value, host or device rate), the 16-byte device
- *    dlrm_sr_state (seed, step) it reads, and dlrm_sr_tick (a one-thread step += 1). */
-#define DLRM_ABI_VERSION 16/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    dlrm_sr_state (seed, step) it reads, and dlrm_sr_tick (a one-thread step += 1).
+ * 17: int8 / int4 embedding tables for inference in the fused engine: dlrm_rows_quantize (the
+ *    row-wise 8- and 4-bit packer on the device, bitwise torch's CPU packers) and
+ *    dlrm_interact_dot_forward_gather_rows (the gather-fused dot interaction reading Q8 / Q4
+ *    rows). */
+#define DLRM_ABI_VERSION 17/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -298,6 +302,32 @@ int dlrm_tbe_forward_rows(const void* weights, int32_t format, int64_t row_bytes
                           int32_t index_bits, const void* offsets, int32_t offset_bits,
                           const float* per_sample_weights, float* out, int64_t out_batch_stride,
                           int32_t* error_flag, dlrm_stream_t stream);
+
+/*
+ * ABI v17.  Row-wise quantizer on the device (DLRM_Net.quantize_embedding,
+ * dlrm_s_pytorch.py:609-625, without the host round trip): src is [rows][D] contiguous fp32
+ * (DLRM_ROWS_F32, 16-byte aligned) or fp16 (DLRM_ROWS_F16, 8-byte aligned; widened exactly,
+ * then treated as fp32); dst is [rows][dst_row_bytes] in DLRM_ROWS_Q8 (4-byte aligned) or
+ * DLRM_ROWS_Q4 (2-byte aligned), dst_row_bytes == dlrm_tbe_row_bytes(dst_format, D) (else
+ * INVALID_ARG).  D % 4 == 0 and D <= 512 (else UNSUPPORTED), the contract of
+ * dlrm_tbe_forward_rows, which reads the result.  rows == 0 launches nothing.  Exactly
+ * rows * dst_row_bytes bytes are written.
+ *
+ * The output is bitwise what torch.ops.quantized.embedding_bag_byte_prepack /
+ * embedding_bag_4bit_prepack return for the same fp32 rows.  Per row, in fp32 with one
+ * rounding per operation (IEEE division, round-half-even rint, no contraction):
+ *   Q8: mn = min, range = max - mn; stored scale = range / 255, stored bias = mn;
+ *       inv = 255 / (range + 1e-8f); q = clamp(rint((x - mn) * inv), 0, 255).
+ *   Q4: mn = fp16(min) (nearest even), range = max - mn; scale = fp16(range / 15), 1 if that
+ *       is 0; inv = 1 / scale (scale = inv = 1 if infinite); q = clamp(rint((x - mn) * inv),
+ *       0, 15); stored fp16 scale, fp16 mn.
+ * Outside the contract (the bits are then unspecified, the bounds still hold): rows holding
+ * NaN, +-Inf or fp32 subnormals, and a non-zero range below 1e-30.  A row whose minimum is
+ * held as both -0 and +0 stores a zero bias of unspecified sign.
+ */
+int dlrm_rows_quantize(const void* src, int32_t src_format, int64_t rows, int64_t D,
+                       int32_t dst_format, void* dst, int64_t dst_row_bytes,
+                       dlrm_stream_t stream);
 
 /*
  * Gradient of the per-sample weights of a weighted lookup (learned weighted pooling,
@@ -554,6 +584,23 @@ int dlrm_interact_dot_backward_gather_f16(int32_t B, int32_t F, int32_t D, const
                                           int32_t self_interaction, const float* grad_out,
                                           int64_t ld_gout, float* const* grad_ptrs,
                                           const int64_t* grad_bstrides, int32_t relu_x,
+                                          dlrm_stream_t stream);
+/*
+ * ABI v17.  The forward gather entry point on row-wise quantized tables (inference; there is
+ * no backward): `weights` is [total rows][row_bytes] bytes in `format` DLRM_ROWS_Q8 or
+ * DLRM_ROWS_Q4 (any other format: UNSUPPORTED; fp32 and fp16 rows keep their entry points),
+ * 16-byte aligned, row_bytes == dlrm_tbe_row_bytes(format, D) (else INVALID_ARG), e.g. what
+ * dlrm_rows_quantize wrote.  A lane reads the levels of its four columns as one 4-byte (Q8)
+ * or 2-byte (Q4) load and the row's scale and bias as one 8-byte or 4-byte load, and forms
+ * fmaf(scale, q, bias): the value dlrm_tbe_forward_rows gives a one-index bag.  Everything
+ * after that is the fp32 kernel, so the result is bitwise dlrm_interact_dot_forward_gather's
+ * on the dequantised table.  Same D, F, dispatch, error flag and statuses.
+ */
+int dlrm_interact_dot_forward_gather_rows(int32_t B, int32_t F, int32_t D, const float* x,
+                                          int64_t x_bstride, const void* weights, int32_t format,
+                                          int64_t row_bytes, const int64_t* row_base,
+                                          const int32_t* indices, int32_t self_interaction,
+                                          float* out, int64_t ld_out, int32_t* error_flag,
                                           dlrm_stream_t stream);
 /* Cat: out[b][f*D:(f+1)*D] = feature f. */
 int dlrm_interact_cat_forward(int32_t B, int32_t F, int32_t D, const float* const* feat_ptrs,
