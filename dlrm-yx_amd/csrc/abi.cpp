@@ -7,7 +7,7 @@
 namespace dlrm {
 namespace {
 thread_local char g_last_error[1024] = {0};
-constexpr int kTuneKeys = 12;
+constexpr int kTuneKeys = 13;
 thread_local int64_t g_tuning[kTuneKeys] = {0};
 }
 
@@ -21,10 +21,19 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
-// ABI v17: the version is only reported by a library that links the entry points it names
+// ABI v17, v18: the version is only reported by a library that links the entry points it names
 // (taking their addresses with the header's types fails the build if one is missing).
-static_assert(DLRM_ABI_VERSION >= 17, "abi.cpp checks the v17 entry points");
+static_assert(DLRM_ABI_VERSION >= 18, "abi.cpp checks the v17 and v18 entry points");
 namespace {
+[[maybe_unused]] int (*const kLinear8Pack)(int64_t, int64_t, const float*, int64_t, int8_t*,
+                                           int64_t, float*, void*, size_t,
+                                           dlrm_stream_t) = &dlrm_linear8_pack;
+[[maybe_unused]] int (*const kLinear8Range)(int64_t, int64_t, const float*, int64_t, float*,
+                                            dlrm_stream_t) = &dlrm_linear8_range;
+[[maybe_unused]] int (*const kLinear8Forward)(int64_t, int64_t, int64_t, const float*, int64_t,
+                                              const float*, const int8_t*, int64_t, const float*,
+                                              const float*, int64_t, int32_t, float*, int64_t,
+                                              float*, dlrm_stream_t) = &dlrm_linear8_forward;
 [[maybe_unused]] int (*const kRowsQuantize)(const void*, int32_t, int64_t, int64_t, int32_t, void*,
                                             int64_t, dlrm_stream_t) = &dlrm_rows_quantize;
 [[maybe_unused]] int (*const kGatherRows)(int32_t, int32_t, int32_t, const float*, int64_t,
@@ -38,7 +47,7 @@ extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }
 extern "C" const char* dlrm_last_error(void) { return dlrm::g_last_error; }
 
 extern "C" int dlrm_set_tuning(int32_t key, int64_t value) {
-  DLRM_ARG(key >= DLRM_TUNE_GEMM_TILE && key <= DLRM_TUNE_LINEAR16_WGRAD_SPLIT,
+  DLRM_ARG(key >= DLRM_TUNE_GEMM_TILE && key <= DLRM_TUNE_LINEAR8_TILE,
            "dlrm_set_tuning: unknown key %d", (int)key);
   DLRM_ARG(value >= 0, "dlrm_set_tuning: negative value");
   dlrm::g_tuning[key] = value;

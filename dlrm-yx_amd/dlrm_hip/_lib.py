@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 17
+ABI_VERSION = 18
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -219,6 +219,14 @@ SIGNATURES = {
     "dlrm_interact_dot_forward_gather_rows": (c_int32, [c_int32, c_int32, c_int32, P, c_int64, P,
                                                         c_int32, c_int64, P, P, c_int32, P,
                                                         c_int64, P, P]),
+    # ABI v18: int8 dynamic-quantized inference Linear (weight packer, activation range, the
+    # forward on the i8 MFMA)
+    "dlrm_linear8_pack_workspace_size": (c_size_t, [c_int64, c_int64]),
+    "dlrm_linear8_pack": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P, P, c_size_t,
+                                    P]),
+    "dlrm_linear8_range": (c_int32, [c_int64, c_int64, P, c_int64, P, P]),
+    "dlrm_linear8_forward": (c_int32, [c_int64, c_int64, c_int64, P, c_int64, P, P, c_int64, P,
+                                       P, c_int64, c_int32, P, c_int64, P, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

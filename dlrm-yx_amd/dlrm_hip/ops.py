@@ -80,7 +80,7 @@ class DeferredErrorCheck:
 # dlrm_tune_key (include/dlrm_hip.h): plan overrides for sweeps and coverage tests
 TUNE_KEYS = {"gemm_tile": 1, "gemm_split": 2, "tbe_block": 3, "tbe_sort": 4, "tbe_lean": 5,
              "interact_bwd": 6, "interact_fwd": 7, "linear16_tile": 8, "linear16_dgrad_tile": 9,
-             "linear16_wgrad_tile": 10, "linear16_wgrad_split": 11}
+             "linear16_wgrad_tile": 10, "linear16_wgrad_split": 11, "linear8_tile": 12}
 
 
 class tuning:
@@ -999,6 +999,109 @@ def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tens
         bstride = bias.stride(0) if N > 1 else 1
     _lib.call("dlrm_linear16_forward", MLP16_TYPES[dtype], M, N, K, _p(x), ldx, _p(W), ldw,
               _p(bias), bstride, int(bool(relu)), _p(out), ldy, _stream(x.device))
+    return out
+
+
+LINEAR8_TILES = LINEAR16_TILES  # DLRM_TUNE_LINEAR8_TILE values
+LINEAR8_RANGE_FLOATS = 2048  # DLRM_LINEAR8_RANGE_FLOATS: min partials, then max partials
+LINEAR8_MAX_K = 131072
+
+
+class Linear8Weights:
+    """The packed weights of one int8 Linear (dlrm_linear8_pack): ``wq`` int8 [N, ldwq] with
+    ldwq a multiple of 64 (columns >= K are 0), ``s_w`` one fp32 scale, both on the device of
+    the fp32 weights."""
+
+    def __init__(self, wq: torch.Tensor, s_w: torch.Tensor, N: int, K: int):
+        if wq.dtype != torch.int8 or wq.dim() != 2 or not wq.is_contiguous() \
+                or wq.shape[0] != N or wq.shape[1] % 64 or wq.shape[1] < max(K, 64):
+            raise ValueError(f"Linear8Weights: wq must be contiguous int8 [{N}, ldwq] with ldwq a "
+                             f"multiple of 64 and >= {max(K, 64)}, not {wq.dtype} "
+                             f"{list(wq.shape)}")
+        if s_w.dtype != torch.float32 or s_w.numel() != 1 or s_w.device != wq.device:
+            raise ValueError("Linear8Weights: s_w must be one fp32 value on wq's device")
+        self.wq, self.s_w, self.N, self.K = wq, s_w, int(N), int(K)
+
+
+def linear8_pack(W: torch.Tensor, out: Optional[Linear8Weights] = None) -> Linear8Weights:
+    """dlrm_linear8_pack: W [N, K] fp32 (a view with contiguous rows: the columns past K of a
+    wider buffer, e.g. a folded bias column, are not read) -> per-tensor symmetric int8 weights,
+    bitwise torch's MinMaxObserver(qint8, per_tensor_symmetric) + quantize_per_tensor.  ``out``:
+    a Linear8Weights of the same N and K to re-pack into (its storage is kept)."""
+    ldw = _row_major(W, "W", "linear8_pack")
+    _check_cuda(W)
+    N, K = W.shape
+    if out is None:
+        ldwq = max((K + 63) // 64 * 64, 64)
+        out = Linear8Weights(torch.zeros((N, ldwq), dtype=torch.int8, device=W.device),
+                             torch.zeros(1, dtype=torch.float32, device=W.device), N, K)
+    elif (out.N, out.K) != (N, K) or out.wq.device != W.device:
+        raise ValueError(f"linear8_pack: out holds [{out.N}, {out.K}] weights, W is [{N}, {K}]")
+    need = _lib.query("dlrm_linear8_pack_workspace_size", N, K)
+    ws = _ws("linear8_pack", need, W.device)
+    _lib.call("dlrm_linear8_pack", N, K, _p(W), ldw, _p(out.wq), out.wq.shape[1], _p(out.s_w),
+              _p(ws), ws.numel(), _stream(W.device))
+    return out
+
+
+def linear8_range(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dlrm_linear8_range: the min / max partials of x [M, K] (fp32, contiguous rows) that
+    linear8_forward folds: LINEAR8_RANGE_FLOATS fp32 values (``out``: such a tensor)."""
+    ldx = _row_major(x, "x", "linear8_range")
+    _check_cuda(x, out)
+    if out is None:
+        out = torch.empty(LINEAR8_RANGE_FLOATS, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.numel() != LINEAR8_RANGE_FLOATS \
+            or not out.is_contiguous():
+        raise ValueError(f"linear8_range: out must be {LINEAR8_RANGE_FLOATS} contiguous fp32")
+    _lib.call("dlrm_linear8_range", x.shape[0], x.shape[1], _p(x), ldx, _p(out),
+              _stream(x.device))
+    return out
+
+
+def linear8_forward(x: torch.Tensor, packed: Linear8Weights,
+                    bias: Optional[torch.Tensor] = None, relu: bool = False,
+                    out: Optional[torch.Tensor] = None, rng: Optional[torch.Tensor] = None,
+                    qparams: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Forward-only int8 Linear (dlrm_linear8_forward): out [M, N] = act(dequant(q(x) Wq^T) +
+    bias), x [M, K] an fp32 tensor or view with contiguous rows quantized per call to 7-bit
+    codes from its own range, bitwise torch's dynamically quantized nn.Linear on fbgemm.
+    ``rng``: linear8_range(x) (computed here when None).  ``bias`` may be a strided 1-D view;
+    only out[:M, :N] is written (``out`` may be a view of a wider buffer); no column >= K of x
+    is read.  ``qparams``: 2 fp32 on the device that receive (s_x, zero point)."""
+    if not isinstance(packed, Linear8Weights):
+        raise ValueError("linear8_forward: packed must be a Linear8Weights (linear8_pack)")
+    ldx = _row_major(x, "x", "linear8_forward")
+    M, K = x.shape
+    N = packed.N
+    if K != packed.K:
+        raise ValueError(f"linear8_forward: x is [{M}, {K}], the packed weights are "
+                         f"[{N}, {packed.K}]")
+    if K > LINEAR8_MAX_K:
+        raise ValueError(f"linear8_forward: K {K} > {LINEAR8_MAX_K}")
+    bstride = 0
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != N or bias.dtype != torch.float32:
+            raise ValueError("linear8_forward: bias must be N fp32 values")
+        bstride = bias.stride(0) if N > 1 else 1
+    if out is not None and (out.dim() != 2 or tuple(out.shape) != (M, N)):
+        raise ValueError(f"linear8_forward: out is {list(out.shape)}, expected [{M}, {N}]")
+    if rng is not None and (rng.dtype != torch.float32 or rng.numel() != LINEAR8_RANGE_FLOATS
+                            or not rng.is_contiguous()):
+        raise ValueError(f"linear8_forward: rng must be {LINEAR8_RANGE_FLOATS} contiguous fp32 "
+                         "(linear8_range)")
+    if qparams is not None and (qparams.dtype != torch.float32 or qparams.numel() != 2
+                                or not qparams.is_contiguous()):
+        raise ValueError("linear8_forward: qparams must be 2 contiguous fp32")
+    _check_cuda(x, packed.wq, bias, out, rng, qparams)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    ldy = _row_major(out, "out", "linear8_forward")
+    if rng is None:
+        rng = linear8_range(x)
+    _lib.call("dlrm_linear8_forward", M, N, K, _p(x), ldx, _p(rng), _p(packed.wq),
+              packed.wq.shape[1], _p(packed.s_w), _p(bias), bstride, int(bool(relu)), _p(out),
+              ldy, _p(qparams), _stream(x.device))
     return out
 
 

@@ -38,6 +38,10 @@ optimizer update.  Layout decisions (MI355X-first):
   predict / capture_predict / evaluate; one GPU, plain tables): a row-wise quantized snapshot
   of the tables packed on the device (C3: 7.4 / 3.7 GB), read by the gather-fused interaction
   or the pooled Q8 / Q4 lookup; the masters stay and the training step never reads it.
+* int8 MLP layers for inference on request (quantize_mlp(8), then mlp_bits=8 on predict /
+  capture_predict / evaluate; one GPU): a per-tensor int8 snapshot of every MLP layer, each
+  run as a range launch plus a dynamically quantized Linear on the i8 MFMA, bitwise torch's
+  quantize_dynamic; slower than the fp32 and bf16 predicts at C3.
 """
 from __future__ import annotations
 
@@ -192,6 +196,14 @@ class _Layer:
     sumb: Optional[torch.Tensor] = None
 
 
+@dataclass
+class _Layer8:
+    """quantize_mlp's snapshot of one layer."""
+    packed: Optional["ops.Linear8Weights"]  # int8 weights + their scale
+    bias: torch.Tensor  # [N] fp32 copy
+    rng: torch.Tensor   # the min / max partials of this layer's input, rewritten by every call
+
+
 class DLRMTrainer:
     def __init__(self, cfg: TrainerConfig, device="cuda:0", rank: int = 0, world_size: int = 1,
                  process_group=None, seed: int = 0, init: bool = True, comm=None,
@@ -284,6 +296,9 @@ class DLRMTrainer:
         # row-wise quantized snapshots of the tables for predict(emb_bits=8 | 4), one buffer per
         # width, filled by quantize_embedding; the training step never reads them
         self._qrows = {}
+        # the int8 snapshot of the MLP layers for predict(mlp_bits=8), filled by quantize_mlp
+        # (DESIGN.md §21): id(layer) -> _Layer8; the training step never reads it
+        self._mlp8 = None
         self.momentum = None
         if cfg.optimizer == "rwsadagrad":
             self.momentum = torch.zeros(max(self.total_rows, 1), dtype=torch.float32,
@@ -830,7 +845,7 @@ class DLRMTrainer:
 
     def _build(self, batch: Batch, profile=None, predict=None):
         """The segment list of the training step (segments) or, ``predict`` = (metrics,
-        precision), of the forward-only pass (predict_segments), from one set of pieces: the
+        precision, emb_bits, mlp_bits), of the forward-only pass (predict_segments), from one set of pieces: the
         context of this call first, then the pieces both lists use, the forward-only list,
         the pieces of the backward and the step's four segment orders.
 
@@ -839,8 +854,12 @@ class DLRMTrainer:
         layer and pass.  Every other piece is the same code for both."""
         cfg = self.cfg
         train = predict is None
-        metrics, precision, emb_bits = (None, cfg.mlp_precision, 32) if train else predict
-        fp32 = precision == "fp32"
+        metrics, precision, emb_bits, mlp_bits = \
+            (None, cfg.mlp_precision, 32, 32) if train else predict
+        # predict's mlp_bits = 8 (DESIGN.md §21): like the 16-bit modes it selects only the MLP
+        # closures below and runs without the fused bottom chain
+        q8 = None if mlp_bits == 32 else self.quantized_mlp(mlp_bits)
+        fp32 = precision == "fp32" and q8 is None
         D = self.D
         Bl = batch.X.shape[0]
         B = Bl * self.world
@@ -920,6 +939,17 @@ class DLRMTrainer:
         if fp32:
             def mlp_fwd(L, h, out, side=False):
                 gemm([self._fwd(L, h, out)], side=side)
+        elif q8 is not None:
+            # int8, dynamically quantized: two launches per layer - the min / max partials of
+            # the input, then the Linear on the i8 MFMA, whose workgroups derive the input's
+            # scale and zero point from the partials themselves (no host read).  The packed
+            # weights and the bias are quantize_mlp's snapshot, not the fp32 masters.
+            def mlp_fwd(L, h, out, side=False, relu=True):
+                with prof("gemm"):
+                    s = q8[id(L)]
+                    ops.linear8_range(h[:, :L.K], out=s.rng)
+                    ops.linear8_forward(h[:, :L.K], s.packed, bias=s.bias, relu=relu,
+                                        out=out[:, :L.N], rng=s.rng)
         else:
             # 16 bit: one launch, relu(r16(h[:, :K]) r16(W[:, :K])^T + b) -> out[:, :N], the
             # operands rounded to nearest-even in flight from the fp32 tensors (no weight
@@ -1051,7 +1081,15 @@ class DLRMTrainer:
                 interaction_fwd()
                 with record_function("module::forward_pass::top_mlp"):
                     h = top_fwd()
-                    ops.head_predict(h[:, :last.Kp], last.W[0, :last.Kp], cfg.loss_threshold,
+                    hx, hw = h[:, :last.Kp], last.W[0, :last.Kp]
+                    if q8 is not None:
+                        # the reference quantizes every nn.Linear: the last one runs as an
+                        # N = 1 int8 layer without ReLU, and the head takes its z as a
+                        # one-column input with weight 1.0 (fmaf(z, 1, 0) and a wave sum with
+                        # zeros: z itself), so the sigmoid, clamp and log stay the head's
+                        mlp_fwd(last, h, ws["z8"], relu=False)
+                        hx, hw = ws["z8"], ws["one8"]
+                    ops.head_predict(hx, hw, cfg.loss_threshold,
                                      prob=ws["prob"],
                                      target=batch.target if metrics is not None else None,
                                      state=metrics)
@@ -1684,16 +1722,72 @@ class DLRMTrainer:
         self.quantized_rows(emb_bits)
         return int(emb_bits)
 
+    def quantize_mlp(self, bits: int) -> None:
+        """Pack every Linear of the bottom and top MLP, the last top layer included, for
+        predict(..., mlp_bits=8): per-tensor symmetric int8 weights (dlrm_linear8_pack, the
+        bias column left out of the range) and a copy of the bias, in engine-owned buffers
+        (the reference's --quantize-mlp-with-bit 8: torch.quantization.quantize_dynamic over
+        every nn.Linear, dlrm_s_pytorch.py:1757-1781).
+
+        A SNAPSHOT, as quantize_embedding's: the fp32 masters stay, training is untouched and
+        does not move the packed layers; a second call re-packs into the same storage, so an
+        already captured predict graph reads the new values."""
+        if bits != 8:
+            raise ValueError(f"quantize_mlp({bits!r}): 8 (16-bit operands need no packing: "
+                             "predict(..., precision='bf16' | 'fp16'))")
+        self._mlp8_refusals()
+        if self._mlp8 is None:
+            self._mlp8 = {}
+        for L in self.layers:
+            s = self._mlp8.get(id(L))
+            if s is None:
+                s = self._mlp8[id(L)] = _Layer8(
+                    packed=None, bias=torch.empty(L.N, dtype=torch.float32, device=self.dev),
+                    rng=torch.zeros(ops.LINEAR8_RANGE_FLOATS, dtype=torch.float32,
+                                    device=self.dev))
+            s.packed = ops.linear8_pack(L.W[:, :L.K], out=s.packed)
+            s.bias.copy_(L.b)
+
+    def _mlp8_refusals(self) -> None:
+        if self.distributed:
+            raise NotImplementedError(
+                "int8 MLP layers on the multi-GPU schedule: they run on one GPU only "
+                "(DESIGN.md §21)")
+
+    def quantized_mlp(self, bits: int = 8) -> dict:
+        """The packed layers of quantize_mlp(bits), keyed by id(layer)."""
+        if bits != 8:
+            raise ValueError(f"mlp_bits {bits!r}: 32 or 8")
+        if self._mlp8 is None:
+            raise RuntimeError("no int8 MLP layers: call quantize_mlp(8) first")
+        return self._mlp8
+
+    def _mlp_bits(self, mlp_bits: int, precision: str) -> int:
+        """Validate predict's ``mlp_bits``: 32 = the ``precision`` path, 8 = the packed
+        snapshot of quantize_mlp(8) (which must exist; fp32 ``precision`` only)."""
+        if mlp_bits == 32:
+            return 32
+        if mlp_bits != 8:
+            raise ValueError(f"mlp_bits {mlp_bits!r}: 32 or 8")
+        if precision != "fp32":
+            raise ValueError(f"mlp_bits=8 with precision={precision!r}: the int8 layers replace "
+                             "the MLP operands' precision; leave precision at 'fp32'")
+        self._mlp8_refusals()
+        self.quantized_mlp(8)
+        return 8
+
     def predict(self, batch: Batch, metrics=None, precision: str = "fp32",
-                emb_bits: int = 32) -> torch.Tensor:
+                emb_bits: int = 32, mlp_bits: int = 32) -> torch.Tensor:
         """Forward only: prob [B_local] for ``batch`` (a device tensor owned by this batch
         size, overwritten by the next predict of it).  Writes no weight, no optimizer
         state, no gradient and no pending launch role; with ``metrics`` (a
         metrics.EvalState) the head also logs every (prob, batch.target) sample.
         ``precision`` "bf16" | "fp16": the MLP layers below the head on the 16-bit MFMA
         (predict_segments).  ``emb_bits`` 8 | 4: the embedding rows from the packed snapshot
-        of quantize_embedding(emb_bits) instead of the master tables."""
-        for _kind, fn in self.predict_segments(batch, metrics, precision, emb_bits):
+        of quantize_embedding(emb_bits) instead of the master tables.  ``mlp_bits`` 8: every
+        MLP layer, the last one included, as a dynamically quantized int8 Linear on the
+        snapshot of quantize_mlp(8)."""
+        for _kind, fn in self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits):
             fn()
         return self._predict_bufs(self._buffers(batch.X.shape[0],
                                                 batch.X.shape[0] * self.world))["prob"]
@@ -1707,12 +1801,15 @@ class DLRMTrainer:
             Bl = bufs["prob"].shape[0]
             pb = bufs["predict"] = {
                 "prob": torch.zeros(Bl, dtype=torch.float32, device=self.dev),
+                # mlp_bits = 8: the last Linear's output and the head's weight for it
+                "z8": torch.zeros((Bl, 1), dtype=torch.float32, device=self.dev),
+                "one8": torch.ones(1, dtype=torch.float32, device=self.dev),
                 "ws": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev),
                 "ws_side": torch.zeros(1 << 20, dtype=torch.uint8, device=self.dev)}
         return pb
 
     def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32",
-                         emb_bits: int = 32):
+                         emb_bits: int = 32, mlp_bits: int = 32):
         """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
         ``segments()`` and built from the same pieces (_build): the lookup
         (dlrm_tbe_forward; nothing of the backward's sort), the bottom MLP (one GPU: beside
@@ -1734,44 +1831,60 @@ class DLRMTrainer:
         gather-fused interaction dequantises them in registers
         (dlrm_interact_dot_forward_gather_rows, still no lookup launch), otherwise the pooled
         lookup is one dlrm_tbe_forward_rows.  It composes with every ``precision`` and with
-        ``metrics``; 32 is the path above, bit for bit."""
+        ``metrics``; 32 is the path above, bit for bit.
+
+        ``mlp_bits`` 8 (the reference's --quantize-mlp-with-bit 8): every
+        bottom- and top-MLP layer runs as dlrm_linear8_range + dlrm_linear8_forward on the
+        packed snapshot quantize_mlp(8) built (RuntimeError without one), bitwise torch's
+        dynamically quantized nn.Linear; the last layer too, as N = 1 without ReLU, and
+        dlrm_head_predict keeps the sigmoid, the clamp and the metric log.  The fused bottom
+        chain is not used.  It needs ``precision`` "fp32" (ValueError otherwise), composes
+        with ``emb_bits`` and ``metrics``, and runs on one GPU only."""
         return self._build(batch, predict=(metrics, _precision(precision),
-                                           self._emb_bits(emb_bits)))
+                                           self._emb_bits(emb_bits),
+                                           self._mlp_bits(mlp_bits, precision)))
 
     def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32",
-                        emb_bits: int = 32):
+                        emb_bits: int = 32, mlp_bits: int = 32):
         """A replayable forward-only pass for ``batch`` (capture()'s modes over
         predict_segments).  Run one eager predict of this batch size first (allocations).
         Each call of the returned callable scores the batch's current contents into the
         tensor predict() returns; with ``metrics`` every call appends B_local samples (the
         log's cursor lives on the device).  ``precision``, ``emb_bits``: as predict_segments
-        (the graph holds the packed buffer's address; quantize_embedding re-packs in place)."""
+        (the graph holds the packed buffer's address; quantize_embedding re-packs in place),
+        ``mlp_bits`` likewise (quantize_mlp re-packs in place)."""
         _precision(precision)
         self._emb_bits(emb_bits)
+        self._mlp_bits(mlp_bits, precision)
         run, _mode, _graphs = self._capture_segments(
-            lambda: self.predict_segments(batch, metrics, precision, emb_bits), pool, None)
+            lambda: self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits),
+            pool, None)
         return run
 
-    def evaluate(self, batches, metrics, precision: str = "fp32", emb_bits: int = 32) -> dict:
+    def evaluate(self, batches, metrics, precision: str = "fp32", emb_bits: int = 32,
+                 mlp_bits: int = 32) -> dict:
         """Score every batch into ``metrics`` (a metrics.EvalState, not reset here) and
         return its compute() dict (on several ranks: over all ranks' samples).  One graph
         per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
         batches are copied into.  Index errors are checked once, at the end.
-        ``precision``, ``emb_bits``: as predict_segments (parts of the graph key)."""
+        ``precision``, ``emb_bits``, ``mlp_bits``: as predict_segments (parts of the graph
+        key)."""
         _precision(precision)
         self._emb_bits(emb_bits)
+        self._mlp_bits(mlp_bits, precision)
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
-                   self._gather_applies(batch), precision, emb_bits)
+                   self._gather_applies(batch), precision, emb_bits, mlp_bits)
             if key not in graphs:
                 fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
                               batch.target.clone(), batch.max_per_table, batch.one_hot)
-                self.predict(fixed, precision=precision,
-                             emb_bits=emb_bits)  # eager, unlogged: allocations
+                self.predict(fixed, precision=precision, emb_bits=emb_bits,
+                             mlp_bits=mlp_bits)  # eager, unlogged: allocations
                 torch.cuda.current_stream(self.dev).synchronize()
                 graphs[key] = (fixed, self.capture_predict(fixed, metrics, precision=precision,
-                                                           emb_bits=emb_bits))
+                                                           emb_bits=emb_bits,
+                                                           mlp_bits=mlp_bits))
             fixed, run = graphs[key]
             fixed.X.copy_(batch.X)
             fixed.offsets.copy_(batch.offsets)

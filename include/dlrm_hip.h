@@ -136,8 +136,12 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 17: int8 / int4 embedding tables for inference in the fused engine: dlrm_rows_quantize (the
  *    row-wise 8- and 4-bit packer on the device, bitwise torch's CPU packers) and
  *    dlrm_interact_dot_forward_gather_rows (the gather-fused dot interaction reading Q8 / Q4
- *    rows). */
-#define DLRM_ABI_VERSION 17/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    rows).
+ * 18: int8 dynamic-quantized MLP layers for inference: dlrm_linear8_pack (+ _workspace_size;
+ *    the per-tensor symmetric weight packer), dlrm_linear8_range (the activation's min / max
+ *    partials) and dlrm_linear8_forward (the Linear on v_mfma_i32_16x16x64_i8), bitwise
+ *    torch.quantization.quantize_dynamic's fbgemm arithmetic + DLRM_TUNE_LINEAR8_TILE. */
+#define DLRM_ABI_VERSION 18/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -172,7 +176,9 @@ const char* dlrm_last_error(void);
  *   DLRM_TUNE_LINEAR16_WGRAD_SPLIT : workgroups that share one tile's reduction over M in
  *                          dlrm_linear16_wgrad (1 = no split; clipped to 32 and to the
  *                          number of 64-row steps); dlrm_linear16_wgrad_workspace_size
- *                          follows the calling thread's overrides (ABI v13) */
+ *                          follows the calling thread's overrides (ABI v13)
+ *   DLRM_TUNE_LINEAR8_TILE : BM * 1000 + BN of dlrm_linear8_forward's workgroup tile, the
+ *                          same four values (ABI v18) */
 enum dlrm_tune_key {
   DLRM_TUNE_GEMM_TILE = 1,
   DLRM_TUNE_GEMM_SPLIT = 2,
@@ -184,7 +190,8 @@ enum dlrm_tune_key {
   DLRM_TUNE_LINEAR16_TILE = 8,
   DLRM_TUNE_LINEAR16_DGRAD_TILE = 9,
   DLRM_TUNE_LINEAR16_WGRAD_TILE = 10,
-  DLRM_TUNE_LINEAR16_WGRAD_SPLIT = 11
+  DLRM_TUNE_LINEAR16_WGRAD_SPLIT = 11,
+  DLRM_TUNE_LINEAR8_TILE = 12
 };
 int dlrm_set_tuning(int32_t key, int64_t value);
 int64_t dlrm_get_tuning(int32_t key);
@@ -913,6 +920,58 @@ int dlrm_linear16_forward(int32_t type, int64_t M, int64_t N, int64_t K,
                           const float* X, int64_t ldx, const float* W, int64_t ldw,
                           const float* bias, int64_t bias_stride, /* NULL: none */
                           int32_t relu, float* Y, int64_t ldy, dlrm_stream_t stream);
+
+/* ---------------------------------------------------- int8 inference Linear -- */
+/*
+ * Forward-only Linear with int8 operands, dynamically quantized (ABI v18): the arithmetic of
+ * torch.quantization.quantize_dynamic(model, {nn.Linear}, torch.qint8) on the fbgemm engine
+ * (the reference's --inference-only --quantize-mlp-with-bit 8, dlrm_s_pytorch.py:1757-1781),
+ * bit for bit.  "fl" is one fp32 rounding; where nothing is said the arithmetic is fp64.
+ *
+ * Weights: static, per tensor, symmetric, zero point 0 - dlrm_linear8_pack, once per snapshot:
+ *   lo = min(min W, 0), hi = max(max W, 0) over W[0:N][0:K] (row stride ldw; columns >= K,
+ *   e.g. a folded bias column, are not read)
+ *   s_w = max(fl(max(-lo, hi) / 127.5), FLT_EPSILON)
+ *   Wq[n][k] = clamp(rint(fl(W[n][k] * fl(1 / s_w))), -128, 127) for k < K, 0 for
+ *   K <= k < ldwq.  ldwq is a multiple of 64 (>= 64, >= K), Wq is 16-byte aligned; s_w is one
+ *   device float.  Two launches (min / max partials into the workspace, then the quantize
+ *   pass, whose workgroups each fold the partials: min and max are exact, so the order does
+ *   not matter); dlrm_linear8_pack_workspace_size gives the workspace's bytes.
+ *
+ * Activations: dynamic, per tensor, per call, 7-bit range (torch's reduce_range = True).
+ * dlrm_linear8_range writes the min / max of X[0:M][0:K] as DLRM_LINEAR8_RANGE_FLOATS floats
+ * of partials (a fixed count, whatever the shape; NaN elements are skipped);
+ * dlrm_linear8_forward folds them in every workgroup and derives, the same sequence in each:
+ *   mn = min(min X, 0), mx = max(max X, 0), scale = (mx - mn) / 127
+ *   fl(scale) == 0 or 1 / fl(scale) infinite: scale = 0.1
+ *   scale < 6.1e-5f: scale = 6.1e-5f and the range is stretched first (mn == 0: mx =
+ *   fl(6.1e-5f * 127); mx == 0: mn = -fl(6.1e-5f * 127); else both times 6.1e-5f / scale)
+ *   z = |mn / scale| < 127 + |mx / scale| ? 0 - mn / scale : 127 - mx / scale
+ *   zp = z < 0 ? 0 : z > 127 ? 127 : rint(z);  s_x = fl(scale), inv = fl(1 / s_x)
+ *   xq = clamp(rint(fma(x, inv, zp)), 0, 255) (the fma rounds once, to fp32; the code 128
+ *   occurs and is kept), d = xq - zp, which lies in [-127, 127] for finite X and is the
+ *   MFMA's int8 operand; elements with k >= K are d = 0 without being read.
+ * Output: acc = sum_k d[m][k] * Wq[n][k] exactly in int32 (K <= 131072, else
+ * DLRM_ERR_UNSUPPORTED), Y[m][n] = fma(float(acc), fl(s_x * s_w), bias[n * bias_stride])
+ * with one rounding (bias == NULL: fl(float(acc) * fl(s_x * s_w))); float(acc) rounds to
+ * nearest even above 2^24; relu != 0: max(., 0).  Only Y[0:M][0:N] is written; no row >= M of
+ * X or >= N of Wq / bias is read.  X takes 16-byte loads when it is 16-byte aligned and ldx a
+ * multiple of 4, element loads otherwise.  qparams_out (optional, device): {s_x, float(zp)}.
+ * No host read, no atomics, no workspace: graph-capturable, and two calls give the same bits.
+ * NaN or Inf in X or W: the result is unspecified (nothing faults).
+ */
+#define DLRM_LINEAR8_RANGE_FLOATS 2048
+size_t dlrm_linear8_pack_workspace_size(int64_t N, int64_t K);
+int dlrm_linear8_pack(int64_t N, int64_t K, const float* W, int64_t ldw, int8_t* Wq,
+                      int64_t ldwq, float* s_w, void* workspace, size_t workspace_bytes,
+                      dlrm_stream_t stream);
+int dlrm_linear8_range(int64_t M, int64_t K, const float* X, int64_t ldx, float* partials,
+                       dlrm_stream_t stream);
+int dlrm_linear8_forward(int64_t M, int64_t N, int64_t K, const float* X, int64_t ldx,
+                         const float* partials, const int8_t* Wq, int64_t ldwq,
+                         const float* s_w, const float* bias, int64_t bias_stride,
+                         int32_t relu, float* Y, int64_t ldy, float* qparams_out,
+                         dlrm_stream_t stream);
 
 /* ------------------------------------------------- 16-bit training Linear --- */
 /*
