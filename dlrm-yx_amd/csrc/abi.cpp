@@ -21,9 +21,9 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
-// ABI v17, v18: the version is only reported by a library that links the entry points it names
+// ABI v17 - v19: the version is only reported by a library that links the entry points it names
 // (taking their addresses with the header's types fails the build if one is missing).
-static_assert(DLRM_ABI_VERSION >= 18, "abi.cpp checks the v17 and v18 entry points");
+static_assert(DLRM_ABI_VERSION >= 19, "abi.cpp checks the v17 - v19 entry points");
 namespace {
 [[maybe_unused]] int (*const kLinear8Pack)(int64_t, int64_t, const float*, int64_t, int8_t*,
                                            int64_t, float*, void*, size_t,
@@ -40,6 +40,12 @@ namespace {
                                           const void*, int32_t, int64_t, const int64_t*,
                                           const int32_t*, int32_t, float*, int64_t, int32_t*,
                                           dlrm_stream_t) = &dlrm_interact_dot_forward_gather_rows;
+[[maybe_unused]] int (*const kTbeAdagrad)(float*, float*, int64_t, const int64_t*, int32_t,
+                                          int32_t, const void*, int32_t, const void*, int32_t,
+                                          int64_t, int64_t, const float*, const float*, int64_t,
+                                          float, const float*, float, int64_t, void*, size_t,
+                                          int32_t*, int32_t,
+                                          dlrm_stream_t) = &dlrm_tbe_backward_adagrad;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

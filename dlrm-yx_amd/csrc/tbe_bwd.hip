@@ -2,7 +2,9 @@
 //
 // Replaces the EmbeddingBag sparse backward + torch.optim.SGD sparse add_ of the
 // reference step (dlrm_s_pytorch.py:1923-1934; exact-SGD TBE of create_emb_batched
-// :321-334) and the sparse branch of RWSAdagrad.step (optim/rwsadagrad.py:92-115).
+// :321-334), the sparse branch of RWSAdagrad.step (optim/rwsadagrad.py:92-115) and
+// torch.optim.Adagrad's sparse step (the reference's --optimizer adagrad, :1642; element-wise
+// mode, one accumulator per weight).
 //
 // Pipeline (all on the caller's stream, no host sync, graph-capturable):
 //  1. keys:    per lookup l, global row row_base[t] + idx[l] (or a sentinel) and its bag;
@@ -987,8 +989,10 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
   if (sort_only) return DLRM_OK;
 
   const bool f16_rows = mode == MODE_SGD_F16 || mode == MODE_SGD_F16_SR;
+  // (element-wise Adagrad: the state rows are read and written like the weight rows)
   const bool vec4 = (D % 4 == 0) &&
                     ((reinterpret_cast<uintptr_t>(W) & (f16_rows ? 7 : 15)) == 0) &&
+                    (mode != MODE_ADAGRAD_ELEM || (reinterpret_cast<uintptr_t>(mom) & 15) == 0) &&
                     ((reinterpret_cast<uintptr_t>(gout) & 15) == 0) && (gbs % 4 == 0);
   const int64_t nchunks = vec4 ? D / 4 : D;
   int lpb = 1;
@@ -1066,6 +1070,8 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
     BY_LPB(VW, MODE_SGD_F16)           \
   } else if (mode == MODE_SGD_F16_SR) {\
     BY_LPB(VW, MODE_SGD_F16_SR)        \
+  } else if (mode == MODE_ADAGRAD_ELEM) {\
+    BY_LPB(VW, MODE_ADAGRAD_ELEM)      \
   } else {                             \
     BY_LPB(VW, MODE_DENSE)             \
   }
@@ -1246,6 +1252,23 @@ extern "C" int dlrm_tbe_backward_rowwise_adagrad_dev(
                       grad_out, grad_batch_stride, 0.f, eps, workspace, workspace_bytes,
                       max_lookups_per_table, error_flag, presorted, nullptr, stream, name, false,
                       lr_dev);
+}
+
+// ABI v19: element-wise Adagrad (torch.optim.Adagrad, dlrm_s_pytorch.py:1642) on the rows
+// the batch touched; state_sum is [total_rows, D] fp32 in the layout of weights.
+extern "C" int dlrm_tbe_backward_adagrad(
+    float* weights, float* state_sum, int64_t D, const int64_t* row_base, int32_t T, int32_t B,
+    const void* indices, int32_t index_bits, const void* offsets, int32_t offset_bits,
+    int64_t num_lookups, int64_t total_rows, const float* per_sample_weights,
+    const float* grad_out, int64_t grad_batch_stride, float lr, const float* lr_dev, float eps,
+    int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes, int32_t* error_flag,
+    int32_t presorted, dlrm_stream_t stream) {
+  DLRM_ARG(state_sum, "dlrm_tbe_backward_adagrad: null state_sum");
+  return bwd_dispatch(MODE_ADAGRAD_ELEM, weights, state_sum, D, row_base, T, B, indices,
+                      index_bits, offsets, offset_bits, num_lookups, total_rows,
+                      per_sample_weights, grad_out, grad_batch_stride, lr_dev ? 0.f : lr, eps,
+                      workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted,
+                      nullptr, stream, "dlrm_tbe_backward_adagrad", false, lr_dev);
 }
 
 extern "C" int dlrm_tbe_backward_dense(float* grad_weights, int64_t D, const int64_t* row_base,

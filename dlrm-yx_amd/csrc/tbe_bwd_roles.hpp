@@ -22,7 +22,18 @@ constexpr int64_t kLongChN = 1 << 18;
 // as fp16, updated in fp32 and stored back rounded to nearest even.
 // MODE_SGD_F16_SR: the same update in every respect but the store, which rounds
 // stochastically (sr16_bits) with the element's draw of the call's (seed, step) stream.
-enum { MODE_SGD = 0, MODE_ADAGRAD = 1, MODE_DENSE = 2, MODE_SGD_F16 = 3, MODE_SGD_F16_SR = 4 };
+// MODE_ADAGRAD_ELEM: element-wise Adagrad (torch.optim.Adagrad): `mom` is the state S,
+// [total_rows, D] fp32 in the layout of W, one accumulator per weight.  The arithmetic is
+// adagrad_kernel's (misc.hip), operation for operation, so a sparse update equals the dense
+// update with the coalesced gradient bit for bit.
+enum {
+  MODE_SGD = 0,
+  MODE_ADAGRAD = 1,
+  MODE_DENSE = 2,
+  MODE_SGD_F16 = 3,
+  MODE_SGD_F16_SR = 4,
+  MODE_ADAGRAD_ELEM = 5
+};
 template <int MODE>
 constexpr bool kF16Rows = MODE == MODE_SGD_F16 || MODE == MODE_SGD_F16_SR;
 template <int MODE>
@@ -84,6 +95,19 @@ __device__ __forceinline__ void wstore(float* __restrict__ W, int64_t row, int64
   }
 }
 
+// One element of the element-wise Adagrad rule: s += g*g; w -= lr * g / (sqrt(s) + eps).
+__device__ __forceinline__ void adagrad_elem(float& w, float& s, float g, float lr, float eps) {
+  s = fmaf(g, g, s);
+  w = fmaf(-lr, g / (sqrtf(s) + eps), w);
+}
+__device__ __forceinline__ void adagrad_elem(float4& w, float4& s, const float4& g, float lr,
+                                             float eps) {
+  adagrad_elem(w.x, s.x, g.x, lr, eps);
+  adagrad_elem(w.y, s.y, g.y, lr, eps);
+  adagrad_elem(w.z, s.z, g.z, lr, eps);
+  adagrad_elem(w.w, s.w, g.w, lr, eps);
+}
+
 // Apply the coalesced gradient g of one row (group-uniform control flow).
 template <int LPB, int VW, int MAXV, int MODE>
 __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __restrict__ mom,
@@ -109,6 +133,19 @@ __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __res
       if (chunk < nchunks) {
         V w = wrow[chunk];
         vadd(w, g[c]);
+        wrow[chunk] = w;
+      }
+    }
+  } else if (MODE == MODE_ADAGRAD_ELEM) {
+    V* srow = reinterpret_cast<V*>(mom + row * D);
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int chunk = gl + c * LPB;
+      if (chunk < nchunks) {
+        V w = wrow[chunk];
+        V s = srow[chunk];
+        adagrad_elem(w, s, g[c], lr, eps);
+        srow[chunk] = s;
         wrow[chunk] = w;
       }
     }
@@ -171,6 +208,21 @@ __device__ __forceinline__ void finalize_row_pf(float* __restrict__ W, float* __
       if (chunk < nchunks) {
         V x = w[c];
         vadd(x, g[c]);
+        wrow[chunk] = x;
+      }
+    }
+  } else if (MODE == MODE_ADAGRAD_ELEM) {
+    // the weight row was prefetched; the state row is read here (a second prefetched row
+    // per gradient row in flight would double the prefetch's registers)
+    V* srow = reinterpret_cast<V*>(mom + row * D);
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int chunk = gl + c * LPB;
+      if (chunk < nchunks) {
+        V x = w[c];
+        V s = srow[chunk];
+        adagrad_elem(x, s, g[c], lr, eps);
+        srow[chunk] = s;
         wrow[chunk] = x;
       }
     }

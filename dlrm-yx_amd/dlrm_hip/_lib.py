@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 18
+ABI_VERSION = 19
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -227,6 +227,11 @@ SIGNATURES = {
     "dlrm_linear8_range": (c_int32, [c_int64, c_int64, P, c_int64, P, P]),
     "dlrm_linear8_forward": (c_int32, [c_int64, c_int64, c_int64, P, c_int64, P, P, c_int64, P,
                                        P, c_int64, c_int32, P, c_int64, P, P]),
+    # ABI v19: element-wise Adagrad fused into the embedding backward (host rate + NULL, or a
+    # device rate; the [rows, D] fp32 accumulator)
+    "dlrm_tbe_backward_adagrad": (c_int32, [P, P, c_int64, P, c_int32, c_int32, P, c_int32, P,
+                                            c_int32, c_int64, c_int64, P, P, c_int64, c_float,
+                                            P, c_float, c_int64, P, c_size_t, P, c_int32, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

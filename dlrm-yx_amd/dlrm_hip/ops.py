@@ -397,13 +397,17 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
                  sr_state: Optional[torch.Tensor] = None) -> None:
     """mode: 'sgd' (fused exact SGD; fp32 or fp16 weights; 'sgd_f16' names the fp16 case and
     refuses fp32 weights), 'rowwise_adagrad' (fused
-    RWSAdagrad) or 'dense' (weights is a gradient buffer to accumulate into).  max_lookups_per_table:
+    RWSAdagrad), 'adagrad' (fused element-wise torch.optim.Adagrad on fp32 weights;
+    ``momentum`` is its "sum" state, contiguous fp32 of the weights' shape, and the result
+    equals 'dense' into a zero buffer followed by adagrad_update over the whole table, bit
+    for bit) or 'dense' (weights is a gradient buffer to accumulate into).  max_lookups_per_table:
     upper bound on any table's lookups (0 = unknown); <= 4096 selects the per-table LDS
     sort (bitwise the same result as the device-wide radix sort).  ``error_flag``: device
     int32 that receives TBE_ERR_INDEX / TBE_ERR_TABLE_CAP bits (see check_tbe_errors).
     ``presorted``: True - the per-table sort ran in tbe_forward_presort; PRESORTED_ANY -
     tbe_backward_sort ran for this batch.  ``lr``: a float, or ('sgd', fp32 or fp16
-    weights, and 'rowwise_adagrad') a 1-element fp32 device tensor read when the kernels run.
+    weights, 'rowwise_adagrad' and 'adagrad') a 1-element fp32 device tensor read when the
+    kernels run.
     ``sr_state`` (fp16 weights only; ops.sr_state): the updated row is stored rounded
     stochastically with the state's (seed, step) stream instead of to nearest even
     (dlrm_tbe_backward_sgd_f16_sr); the state is read when the kernels run, never written."""
@@ -453,6 +457,18 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
         _lib.call("dlrm_tbe_backward_rowwise_adagrad", _p(weights), _p(momentum), *args_common,
                   lr, eps, mx, _p(workspace), workspace.numel(), _p(error_flag), int(presorted),
                   st)
+    elif mode == "adagrad":
+        if weights.dtype != torch.float32:
+            raise ValueError("tbe_backward: mode 'adagrad' takes fp32 weights")
+        if (momentum is None or momentum.dtype != torch.float32
+                or tuple(momentum.shape) != tuple(weights.shape)
+                or not momentum.is_contiguous()):
+            raise ValueError("tbe_backward: mode 'adagrad' takes its state as momentum=, a "
+                             f"contiguous fp32 tensor of the weights' shape "
+                             f"{tuple(weights.shape)}")
+        _lib.call("dlrm_tbe_backward_adagrad", _p(weights), _p(momentum), *args_common,
+                  0.0 if lr_dev is not None else lr, lr_dev, eps, mx, _p(workspace),
+                  workspace.numel(), _p(error_flag), int(presorted), st)
     elif mode == "dense":
         _lib.call("dlrm_tbe_backward_dense", _p(weights), *args_common, mx, _p(workspace),
                   workspace.numel(), _p(error_flag), int(presorted), st)

@@ -5,7 +5,8 @@ but keeps its state on the GPU — the reference allocates it on the CPU and the
 therefore refuses rwsadagrad on GPU (dlrm_s_pytorch.py:1636-1637).  Sparse gradients
 (COO, possibly uncoalesced, as nn.EmbeddingBag(sparse=True) produces them) are coalesced
 and applied by the deterministic sorted TBE backward kernel in row-wise Adagrad mode;
-dense gradients use the elementwise Adagrad kernel.
+dense gradients use the elementwise Adagrad kernel.  ``Adagrad`` is torch.optim.Adagrad the
+same way, with one accumulator per weight (the TBE backward's element-wise mode).
 """
 from __future__ import annotations
 
@@ -107,6 +108,71 @@ class RWSAdagrad(Optimizer):
                     rb = torch.tensor([0, p.shape[0]], dtype=torch.int64, device=p.device)
                     ops.tbe_backward("rowwise_adagrad", p.data, rb, 1, n, idx, off, vals,
                                      lr=clr, eps=group["eps"], momentum=st["momentum"])
+                else:
+                    ops.adagrad_update(p.data, grad.contiguous(), st["sum"], clr, group["eps"])
+        return loss
+
+
+class Adagrad(Optimizer):
+    """torch.optim.Adagrad (same constructor, same state names "sum" and "step") on the HIP
+    kernels: the reference's ``--optimizer adagrad`` (dlrm_s_pytorch.py:1642), which its driver
+    refuses on a GPU (:1636-1637).  Sparse gradients are coalesced and applied by the
+    deterministic sorted TBE backward kernel in element-wise Adagrad mode (each lookup its
+    own bag); dense gradients use the elementwise Adagrad kernel.  Both are the same
+    arithmetic, so a sparse step equals the dense step on the coalesced gradient bit for
+    bit."""
+
+    def __init__(self, params, lr=1e-2, lr_decay=0.0, weight_decay=0.0,
+                 initial_accumulator_value=0.0, eps=1e-10):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= lr_decay:
+            raise ValueError("Invalid lr_decay value: {}".format(lr_decay))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if not 0.0 <= initial_accumulator_value:
+            raise ValueError("Invalid initial_accumulator_value value: {}".format(
+                initial_accumulator_value))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps,
+                                      weight_decay=weight_decay,
+                                      initial_accumulator_value=initial_accumulator_value))
+        for group in self.param_groups:
+            for p in group["params"]:
+                # a host fp32 scalar tensor, as torch.optim.Adagrad keeps it (state_dict)
+                self.state[p]["step"] = torch.tensor(0.0, dtype=torch.float32)
+                self.state[p]["sum"] = torch.full_like(
+                    p.data, group["initial_accumulator_value"], dtype=torch.float32,
+                    memory_format=torch.contiguous_format)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                grad = p.grad
+                st["step"] += 1
+                if group["weight_decay"] != 0:
+                    if grad.is_sparse:
+                        raise RuntimeError("weight_decay option is not compatible with sparse "
+                                           "gradients")
+                    grad = grad.add(p.data, alpha=group["weight_decay"])
+                clr = group["lr"] / (1.0 + (float(st["step"]) - 1.0) * group["lr_decay"])
+                if grad.is_sparse:
+                    idx = grad._indices()[0]
+                    vals = grad._values().contiguous()
+                    n = idx.numel()
+                    if n == 0:
+                        continue
+                    # each lookup its own bag: T=1, B=nnz, offsets = 0..nnz
+                    off = torch.arange(n + 1, dtype=torch.int64, device=p.device)
+                    rb = torch.tensor([0, p.shape[0]], dtype=torch.int64, device=p.device)
+                    ops.tbe_backward("adagrad", p.data, rb, 1, n, idx, off, vals, lr=clr,
+                                     eps=group["eps"], momentum=st["sum"])
                 else:
                     ops.adagrad_update(p.data, grad.contiguous(), st["sum"], clr, group["eps"])
         return loss

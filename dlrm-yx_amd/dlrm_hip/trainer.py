@@ -83,7 +83,9 @@ class TrainerConfig:
     loss_threshold: float = 0.0
     learning_rate: float = 0.01
     emb_learning_rate: Optional[float] = None  # default: learning_rate
-    optimizer: str = "sgd"         # sgd | rwsadagrad
+    # sgd | rwsadagrad | adagrad (torch.optim.Adagrad, the reference's --optimizer adagrad:
+    # one accumulator per weight, the tables' in a second [rows, D] fp32 buffer)
+    optimizer: str = "sgd"
     adagrad_eps: float = 1e-10
     sharder: str = "greedy"
     allocation: Optional[Sequence[int]] = None
@@ -157,6 +159,10 @@ class TrainerConfig:
             raise ValueError("emb_rounding='stochastic' rounds the fp16 tables' update: it "
                              "needs emb_precision='fp16'")
         if self.emb_precision == "fp16":
+            if self.optimizer == "adagrad":
+                raise NotImplementedError(
+                    "emb_precision='fp16' with optimizer='adagrad': the element-wise Adagrad "
+                    "update takes fp32 tables and an fp32 accumulator (DESIGN.md §22)")
             if self.optimizer == "rwsadagrad":
                 raise NotImplementedError(
                     "emb_precision='fp16' with optimizer='rwsadagrad': there is no fp16 "
@@ -300,9 +306,14 @@ class DLRMTrainer:
         # (DESIGN.md §21): id(layer) -> _Layer8; the training step never reads it
         self._mlp8 = None
         self.momentum = None
+        self.emb_sum = None
         if cfg.optimizer == "rwsadagrad":
             self.momentum = torch.zeros(max(self.total_rows, 1), dtype=torch.float32,
                                         device=self.dev)
+        elif cfg.optimizer == "adagrad":
+            # torch.optim.Adagrad's state['sum'] of the tables: one accumulator per weight
+            self.emb_sum = torch.zeros((max(self.total_rows, 1), D), dtype=torch.float32,
+                                       device=self.dev)
         elif cfg.optimizer != "sgd":
             raise ValueError(f"optimizer {cfg.optimizer!r} not supported")
         # ---- dense parameters: one flat bucket
@@ -325,9 +336,11 @@ class DLRMTrainer:
         sizes = [n * _pad4(k + 1) for n, k in specs]
         self.n_params = int(sum(sizes))
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.dev)
+        # (both Adagrad modes: gradient bucket + dense Adagrad over it)
+        dense_adagrad = cfg.optimizer in ("rwsadagrad", "adagrad")
         self.grads = torch.zeros_like(self.params) if (self.distributed or
-                                                      cfg.optimizer == "rwsadagrad") else None
-        self.adagrad_sum = torch.zeros_like(self.params) if cfg.optimizer == "rwsadagrad" else None
+                                                      dense_adagrad) else None
+        self.adagrad_sum = torch.zeros_like(self.params) if dense_adagrad else None
         self.layers: List[_Layer] = []
         o = 0
         for n, k in specs:
@@ -523,11 +536,18 @@ class DLRMTrainer:
             raise ValueError("no row-wise momentum: optimizer is not rwsadagrad")
         return self._table_views(self.momentum, t)
 
+    def table_sum(self, t: int):
+        """Element-wise Adagrad's accumulator of local table t, shaped like table(t) (a
+        (quotient, remainder) pair for a QR table): torch.optim.Adagrad's state['sum']."""
+        if self.emb_sum is None:
+            raise ValueError("no element-wise Adagrad state: optimizer is not adagrad")
+        return self._table_views(self.emb_sum, t)
+
     def dense_adagrad_state(self):
         """Per layer (sum of squared W gradients [N, K], of b [N]): the dense branch's
-        state['sum'] of RWSAdagrad (optim/rwsadagrad.py:116-119)."""
+        state['sum'] of RWSAdagrad (optim/rwsadagrad.py:116-119) and of torch.optim.Adagrad."""
         if self.adagrad_sum is None:
-            raise ValueError("no Adagrad state: optimizer is not rwsadagrad")
+            raise ValueError("no Adagrad state: optimizer is not rwsadagrad or adagrad")
         out, o = [], 0
         for L in self.layers:
             S = self.adagrad_sum[o:o + L.N * L.Kp].view(L.N, L.Kp)
@@ -900,8 +920,9 @@ class DLRMTrainer:
         c_fwd = conc and "fwd" in overlaps
         c_bot = conc and "bot" in overlaps
         # the embedding update's passes, the head's finalize pass as roles of GEMM launches
+        # (element-wise Adagrad is no launch role either: its update runs as launches of its own)
         tbe_role = (plain and self.tbe_role and profile is None
-                    and self.weights.dtype == torch.float32)
+                    and self.weights.dtype == torch.float32 and self.emb_sum is None)
         head_role = plain and self.head_role and profile is None and len(self.top) > 1
         fuse_bottom = fp32 and self.fuse_bottom
         if train:
@@ -1349,6 +1370,9 @@ class DLRMTrainer:
                     mode = "rowwise_adagrad" if cfg.optimizer == "rwsadagrad" else "sgd"
                     if f16:
                         mode = "sgd_f16"
+                    emb_state = self.momentum
+                    if self.emb_sum is not None:
+                        mode, emb_state = "adagrad", self.emb_sum
                     idx, off = st["csr"]
                     grad = bufs["dE"]
                     if self.qr_active:
@@ -1360,7 +1384,7 @@ class DLRMTrainer:
                     s1 = st.pop("sorted", None)
                     if s1 is not None:  # join the early sort
                         torch.cuda.current_stream(self.dev).wait_stream(s1)
-                    kw = dict(lr=elr, eps=cfg.adagrad_eps, momentum=self.momentum,
+                    kw = dict(lr=elr, eps=cfg.adagrad_eps, momentum=emb_state,
                               grad_batch_stride=grad.stride(0),
                               workspace=self._ws_tbe(idx.numel()),
                               max_lookups_per_table=batch.max_per_table,

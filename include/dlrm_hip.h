@@ -24,6 +24,8 @@
  *                                TBE backward of create_emb_batched (dlrm_s_pytorch.py:321-334)
  *   dlrm_tbe_backward_rowwise_adagrad
  *                             <- RWSAdagrad.step sparse branch (optim/rwsadagrad.py:92-115)
+ *   dlrm_tbe_backward_adagrad <- torch.optim.Adagrad.step on sparse embedding gradients, the
+ *                                reference's --optimizer adagrad (dlrm_s_pytorch.py:1642)
  *   dlrm_qr_split_indices / dlrm_qr_combine_* <- QREmbeddingBag.forward
  *                                (tricks/qr_embedding_bag.py:156-174)
  *   dlrm_interact_dot_*       <- DLRM_Net.interact_features, "dot" branch
@@ -140,8 +142,11 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 18: int8 dynamic-quantized MLP layers for inference: dlrm_linear8_pack (+ _workspace_size;
  *    the per-tensor symmetric weight packer), dlrm_linear8_range (the activation's min / max
  *    partials) and dlrm_linear8_forward (the Linear on v_mfma_i32_16x16x64_i8), bitwise
- *    torch.quantization.quantize_dynamic's fbgemm arithmetic + DLRM_TUNE_LINEAR8_TILE. */
-#define DLRM_ABI_VERSION 18/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    torch.quantization.quantize_dynamic's fbgemm arithmetic + DLRM_TUNE_LINEAR8_TILE.
+ * 19: element-wise Adagrad fused into the embedding backward: dlrm_tbe_backward_adagrad
+ *    (torch.optim.Adagrad's sparse step on a [total_rows, D] fp32 accumulator, host or
+ *    device rate). */
+#define DLRM_ABI_VERSION 19/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -1144,6 +1149,36 @@ int dlrm_tbe_backward_sgd_f16_sr(void* weights, int64_t D, const int64_t* row_ba
                                  size_t workspace_bytes, int32_t* error_flag, int32_t presorted,
                                  dlrm_stream_t stream);
 int dlrm_sr_tick(uint64_t* sr_state, dlrm_stream_t stream);
+/*
+ * Element-wise Adagrad fused into the embedding backward (ABI v19): torch.optim.Adagrad with
+ * sparse gradients, the reference's `--optimizer adagrad` (dlrm_s_pytorch.py:1642; lr_decay =
+ * 0, weight_decay = 0).  state_sum is torch's "sum" state: [total_rows, D] fp32 in the layout
+ * of weights, one accumulator per weight.  The lookups are sorted and their gradients
+ * coalesced per row exactly as in dlrm_tbe_backward_rowwise_adagrad (same sort, same run
+ * order, same Kahan-compensated sums); then, for every element d of every row the call
+ * touched, with g the coalesced gradient:
+ *   s = fmaf(g, g, state_sum[row, d]);   state_sum[row, d] = s;
+ *   weights[row, d] = fmaf(-lr, g / (sqrtf(s) + eps), weights[row, d]);
+ * which is dlrm_adagrad_update's arithmetic operation for operation: the tables after this
+ * call equal, bit for bit, the tables after dlrm_tbe_backward_dense into a zero buffer
+ * followed by dlrm_adagrad_update over the whole table.  Rows the call does not touch keep
+ * their weights and state.  The float4 kernels additionally need state_sum 16-byte aligned
+ * (else the scalar kernels run: same result).
+ *
+ * lr_dev == NULL: the host `lr` is used; else the device fp32 replaces it (as
+ * dlrm_gemm_problem.alpha_dev).  A NULL state_sum is DLRM_ERR_INVALID_ARG.  The workspace is
+ * dlrm_tbe_backward_workspace_size's.  The update is not a launch role
+ * (dlrm_tbe_backward_defer takes modes 0 and 1 only).
+ */
+int dlrm_tbe_backward_adagrad(float* weights, float* state_sum, int64_t D,
+                              const int64_t* row_base, int32_t T, int32_t B,
+                              const void* indices, int32_t index_bits, const void* offsets,
+                              int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
+                              const float* per_sample_weights, const float* grad_out,
+                              int64_t grad_batch_stride, float lr, const float* lr_dev,
+                              float eps, int64_t max_lookups_per_table, void* workspace,
+                              size_t workspace_bytes, int32_t* error_flag, int32_t presorted,
+                              dlrm_stream_t stream);
 int dlrm_tbe_backward_rowwise_adagrad_dev(float* weights, float* momentum, int64_t D,
                                           const int64_t* row_base, int32_t T, int32_t B,
                                           const void* indices, int32_t index_bits,
