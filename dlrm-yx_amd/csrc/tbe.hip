@@ -17,6 +17,7 @@
 //    partials combined in block order; every weight row read and written once — bitwise
 //    reproducible.
 #include "tbe_common.hpp"
+#include "tbe_dispatch.hpp"
 
 namespace {
 
@@ -185,48 +186,23 @@ __global__ __launch_bounds__(256) void csr_from_tables_kernel(int T, int B, CsrA
 
 // ------------------------------------------------------------- dispatch ----
 template <typename IdxT, typename OffT>
-int launch_fwd(const float* W, int64_t D, const int64_t* row_base, int T, int B, const void* idx,
-               const void* off, const float* psw, float* out, int64_t out_bs, int32_t* err,
+int launch_fwd(const float* W, int64_t D, const int64_t* row_base, int T, int B, const IdxT* idx,
+               const OffT* off, const float* psw, float* out, int64_t out_bs, int32_t* err,
                hipStream_t st) {
   const bool vec4 = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(W) & 15) == 0) &&
                     ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (out_bs % 4 == 0);
-  const int64_t nchunks = vec4 ? D / 4 : D;
-  int lpb = 1;
-  while (lpb < nchunks && lpb < 64) lpb <<= 1;
-  const int64_t maxv = dlrm::ceil_div(nchunks, lpb);
-  DLRM_REQUIRE(maxv <= 8, DLRM_ERR_UNSUPPORTED, "tbe_forward: D=%lld too large",
+  const LaneGeom g = lane_geom(vec4 ? D / 4 : D);
+  DLRM_REQUIRE(g.maxv <= 8, DLRM_ERR_UNSUPPORTED, "tbe_forward: D=%lld too large",
                (long long)D);
-  const int64_t nbags = (int64_t)T * B;
-  const int gpw = 64 / lpb;
-  int64_t blocks = dlrm::ceil_div(dlrm::ceil_div(nbags, gpw), 4);
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  const IdxT* ip = static_cast<const IdxT*>(idx);
-  const OffT* op = static_cast<const OffT*>(off);
-#define FWD(LPB, VW, MV)                                                                   \
-  hipLaunchKernelGGL((tbe_fwd_kernel<LPB, VW, MV, IdxT, OffT>), dim3(blocks), dim3(256), 0, \
-                     st, W, D, row_base, T, B, ip, op, psw, out, out_bs, err)
-#define FWD_LPB(VW)                        \
-  switch (lpb) {                           \
-    case 1: FWD(1, VW, 1); break;          \
-    case 2: FWD(2, VW, 1); break;          \
-    case 4: FWD(4, VW, 1); break;          \
-    case 8: FWD(8, VW, 1); break;          \
-    case 16: FWD(16, VW, 1); break;        \
-    case 32: FWD(32, VW, 1); break;        \
-    default:                               \
-      if (maxv == 1) FWD(64, VW, 1);       \
-      else if (maxv == 2) FWD(64, VW, 2);  \
-      else if (maxv <= 4) FWD(64, VW, 4);  \
-      else FWD(64, VW, 8);                 \
-  }
-  if (vec4) {
-    FWD_LPB(4)
-  } else {
-    FWD_LPB(1)
-  }
-#undef FWD_LPB
-#undef FWD
+  const int64_t blocks = lane_blocks((int64_t)T * B, g.lpb, 4);
+  for_row_width(vec4, [&](auto vw) {
+    constexpr int VW = decltype(vw)::value;
+    for_lanes<1, 8>(g, [&](auto lpb, auto mv) {
+      hipLaunchKernelGGL(
+          (tbe_fwd_kernel<decltype(lpb)::value, VW, decltype(mv)::value, IdxT, OffT>),
+          dim3(blocks), dim3(256), 0, st, W, D, row_base, T, B, idx, off, psw, out, out_bs, err);
+    });
+  });
   DLRM_LAUNCH_CHECK("dlrm_tbe_forward");
   return DLRM_OK;
 }
@@ -247,17 +223,10 @@ extern "C" int dlrm_tbe_forward(const float* weights, int64_t D, const int64_t* 
            "dlrm_tbe_forward: offset_bits must be 32|64");
   DLRM_ARG(out_batch_stride >= (int64_t)T * D, "dlrm_tbe_forward: out_batch_stride < T*D");
   hipStream_t st = dlrm::as_stream(stream);
-  if (index_bits == 32 && offset_bits == 32)
-    return launch_fwd<int32_t, int32_t>(weights, D, row_base, T, B, indices, offsets,
-                                        per_sample_weights, out, out_batch_stride, error_flag, st);
-  if (index_bits == 32)
-    return launch_fwd<int32_t, int64_t>(weights, D, row_base, T, B, indices, offsets,
-                                        per_sample_weights, out, out_batch_stride, error_flag, st);
-  if (offset_bits == 32)
-    return launch_fwd<int64_t, int32_t>(weights, D, row_base, T, B, indices, offsets,
-                                        per_sample_weights, out, out_batch_stride, error_flag, st);
-  return launch_fwd<int64_t, int64_t>(weights, D, row_base, T, B, indices, offsets,
-                                      per_sample_weights, out, out_batch_stride, error_flag, st);
+  return for_csr_widths(index_bits, offset_bits, [&](auto i, auto o) {
+    return launch_fwd(weights, D, row_base, T, B, i.ptr(indices), o.ptr(offsets),
+                      per_sample_weights, out, out_batch_stride, error_flag, st);
+  });
 }
 
 // Table-batched QR (the fused engine's QR tables): logical CSR -> physical CSR.  Physical
@@ -374,15 +343,11 @@ extern "C" int dlrm_qr_expand_csr(int32_t T_phys, int32_t B, const void* indices
   if (bx > 4096) bx = 4096;  // grid-stride beyond
   const dim3 grid((unsigned)bx, (unsigned)T_phys), block(256);
   hipStream_t st = dlrm::as_stream(stream);
-#define QX(I, O)                                                                              \
-  hipLaunchKernelGGL((qr_expand_kernel<I, O>), grid, block, 0, st, T_phys, B,                  \
-                     static_cast<const I*>(indices), static_cast<const O*>(offsets), src, kind, \
-                     coll, phys_indices, phys_offsets, phys_capacity, error_flag)
-  if (index_bits == 32 && offset_bits == 32) QX(int32_t, int32_t);
-  else if (index_bits == 32) QX(int32_t, int64_t);
-  else if (offset_bits == 32) QX(int64_t, int32_t);
-  else QX(int64_t, int64_t);
-#undef QX
+  for_csr_widths(index_bits, offset_bits, [&](auto i, auto o) {
+    hipLaunchKernelGGL((qr_expand_kernel<width_t<decltype(i)>, width_t<decltype(o)>>), grid, block,
+                       0, st, T_phys, B, i.ptr(indices), o.ptr(offsets), src, kind, coll,
+                       phys_indices, phys_offsets, phys_capacity, error_flag);
+  });
   DLRM_LAUNCH_CHECK("dlrm_qr_expand_csr");
   return DLRM_OK;
 }
@@ -541,16 +506,12 @@ extern "C" int dlrm_tbe_psw_grad(const float* weights, int64_t D, const int64_t*
   int64_t blocks = dlrm::ceil_div(num_lookups, 4);
   if (blocks > 16384) blocks = 16384;
   hipStream_t st = dlrm::as_stream(stream);
-#define PG(I, O)                                                                             \
-  hipLaunchKernelGGL((tbe_psw_grad_kernel<I, O>), dim3(blocks), dim3(256), 0, st, weights, D, \
-                     row_base, T, B, static_cast<const I*>(indices),                          \
-                     static_cast<const O*>(offsets), num_lookups, grad_out, grad_batch_stride, \
-                     grad_per_sample_weights)
-  if (index_bits == 32 && offset_bits == 32) PG(int32_t, int32_t);
-  else if (index_bits == 32) PG(int32_t, int64_t);
-  else if (offset_bits == 32) PG(int64_t, int32_t);
-  else PG(int64_t, int64_t);
-#undef PG
+  for_csr_widths(index_bits, offset_bits, [&](auto i, auto o) {
+    hipLaunchKernelGGL((tbe_psw_grad_kernel<width_t<decltype(i)>, width_t<decltype(o)>>),
+                       dim3(blocks), dim3(256), 0, st, weights, D, row_base, T, B, i.ptr(indices),
+                       o.ptr(offsets), num_lookups, grad_out, grad_batch_stride,
+                       grad_per_sample_weights);
+  });
   DLRM_LAUNCH_CHECK(name);
   return DLRM_OK;
 }

@@ -27,12 +27,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <utility>
 
 #include "mlp_rows.hpp"
 #include "tbe_bwd_roles.hpp"
 #include "tbe_sort.hpp"
 #include "tbe_common.hpp"
+#include "tbe_dispatch.hpp"
 
 namespace {
 
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(kMlpWaves * 64) void mlp_chain_kernel(const MlpChai
 
 
 // The per-table LDS sort applies (and dlrm_tbe_forward_presort can run it early).
-inline bool presort_applies(size_t key_bytes, int64_t max_seg, int64_t N) {
-  return key_bytes == 4 && max_seg > 0 && max_seg <= kSegCap && N < (int64_t)0x7fffffff;
+inline bool presort_applies(int64_t max_seg, int64_t N) {
+  return max_seg > 0 && max_seg <= kSegCap && N < (int64_t)0x7fffffff;
 }
 
 inline int bit_width_u64(uint64_t v) {
@@ -764,19 +764,92 @@ inline int tiled_digit_bits(int bits) {
   return (bits + 9) / 10 < (bits + 7) / 8 ? 10 : 8;
 }
 
-template <typename IdxT, typename OffT, int DB>
-void launch_tiled_sort(const IdxT* idx, const OffT* off, const int64_t* row_base, int T, int B,
-                       int J, int bits, uint32_t* k_a, int32_t* p_a, uint32_t* k_out,
-                       int32_t* p_out, uint32_t* hist, uint32_t sentinel, int32_t* err,
-                       int off_bits, const int32_t* bag_of, const KeysArgs& keys,
-                       hipStream_t st) {
-  const int npass = (bits + DB - 1) / DB;
+// The one place that turns a digit width into a template argument: f(int_tag<10 | 8>).
+template <class F>
+auto for_digit_bits(int db, F&& f) {
+  return db == 10 ? f(int_tag<10>{}) : f(int_tag<8>{});
+}
+
+// ------------------------------------------------------------------ host path --
+// One backward call as its entry point received it.  Every extern "C" entry point fills
+// this by field name and adds the checks that are its own; everything below it takes the
+// struct, so no list of same-typed neighbours (lr / eps, T / B, weights / momentum) is
+// restated by hand.
+struct BwdCall {
+  const char* name;  // the entry point, for its messages
+  int mode;          // MODE_* of the update (the sort-only entry has none)
+  float* W;          // the weight rows (fp16 rows behind the cast) or the dense gradient buffer
+  float* mom;        // row-wise momentum, element-wise state, or null
+  int64_t D;
+  const int64_t* row_base;
+  int T, B;
+  const void* idx;
+  int index_bits;
+  const void* off;
+  int offset_bits;
+  int64_t N, total_rows;
+  const float* psw;
+  const float* gout;
+  int64_t gbs;
+  float lr;             // the host rate; 0 where lr_dev replaces it
+  const float* lr_dev;  // null, or the device fp32 read when the kernels run
+  float eps;
+  void* ws;
+  size_t ws_bytes;
+  int64_t max_seg;  // the caller's bound on any table's lookups (0: unknown)
+  int32_t* err;
+  int presorted;
+  LaunchRole* role;  // non-null: the update's passes are deferred into this role
+  const uint64_t* sr_state;
+  dlrm_stream_t stream;
+};
+
+struct BwdWs {
+  uint32_t* keys_in;
+  uint32_t* keys_out;
+  int32_t* pos_in;
+  int32_t* pos_out;
+  int32_t* bag_of;
+  float* partial;  // block partials; the sorts' digit histograms before the block kernel
+  size_t partial_words;
+  size_t total;
+};
+
+BwdWs carve_bwd_ws(void* base, int64_t N, int64_t D) {
+  BwdWs w{};
+  WsCarver c(base);
+  w.keys_in = c.take<uint32_t>(N);
+  w.keys_out = c.take<uint32_t>(N);
+  w.pos_in = c.take<int32_t>(N);
+  w.pos_out = c.take<int32_t>(N);
+  w.bag_of = c.take<int32_t>(N);
+  const size_t part = (size_t)2 * ((N + CH - 1) / CH) * D;
+  // global sort, 10-bit digits: per-tile counts + the scan's chunk sums
+  const size_t hist = (size_t)((N + kTile - 1) / kTile) * 1024 + (size_t)kMaxScanChunks * 1024;
+  w.partial_words = part > hist ? part : hist;
+  w.partial = c.take<float>(w.partial_words);
+  w.total = c.used + 256;
+  return w;
+}
+
+// The tiled per-table sort of call c: J tiles per table, the digit histograms in the block
+// kernel's partial buffer (free until the sort is done).  `bags`: see TiledPass::bag_of.
+template <int DB, typename IdxT, typename OffT>
+void launch_tiled_sort(const BwdCall& c, const IdxT* idx, const OffT* off, const BwdWs& w, int J,
+                       const int32_t* bags, hipStream_t st) {
+  const int T = c.T;
+  const int off_bits = (int)sizeof(OffT) * 8;
+  const uint32_t sentinel = (uint32_t)c.total_rows;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w.partial);
+  const KeysArgs keys{c.row_base, T, c.B, c.N, sentinel, w.keys_out, w.pos_out, w.bag_of, c.err,
+                      keys_grid(T, c.B)};
+  const int npass = (bit_width_u64((uint64_t)c.total_rows) + DB - 1) / DB;
   TiledPass a{};
-  a.row_base = row_base, a.T = T, a.B = B, a.J = J, a.hist = hist, a.sentinel = sentinel;
-  a.err = err;
-  a.bag_of = bag_of;
-  // per-table ping-pong (pass_view): each table's own last pass lands in (k_out, p_out)
-  a.ka = k_a, a.pa = p_a, a.ko = k_out, a.po = p_out;
+  a.row_base = c.row_base, a.T = T, a.B = c.B, a.J = J, a.hist = hist, a.sentinel = sentinel;
+  a.err = c.err;
+  a.bag_of = bags;
+  // per-table ping-pong (pass_view): each table's own last pass lands in (keys_out, pos_out)
+  a.ka = w.keys_in, a.pa = w.pos_in, a.ko = w.keys_out, a.po = w.pos_out;
   a.npass = npass;
   plan_scan_chunks(a);
   a.csum = hist + (size_t)T * J * (1 << DB);  // after the per-tile counts
@@ -817,21 +890,23 @@ void launch_tiled_sort(const IdxT* idx, const OffT* off, const int64_t* row_base
 // The device-wide sort (no max_lookups_per_table bound): the tiled passes over ONE segment,
 // the whole lookup array [0, N), of global keys (row_base[t] + row; sentinel for invalid
 // and outside-bag lookups, written with their positions by the keys kernel into (k_x,
-// p_x)).  Passes ping-pong between (k_x, p_x) and (k_y, p_y); returns true when the sorted
-// pairs end in (k_y, p_y).  Stable: equal keys stay in position order, as a stable
-// device-wide radix sort leaves them.
-template <typename IdxT, typename OffT, int DB>
-bool launch_global_sort(const IdxT* idx, const OffT* off, const int64_t* row_base, int64_t N,
-                        int bits, uint32_t* k_x, int32_t* p_x, uint32_t* k_y, int32_t* p_y,
-                        uint32_t* hist, uint32_t sentinel, int32_t* err, const int32_t* bag_of,
-                        hipStream_t st) {
-  const int npass = (bits + DB - 1) / DB;
+// p_x) = (keys_in, pos_in)).  Passes ping-pong between (k_x, p_x) and (k_y, p_y) =
+// (keys_out, pos_out); returns true when the sorted pairs end in (k_y, p_y).  Stable: equal
+// keys stay in position order, as a stable device-wide radix sort leaves them.
+template <int DB, typename IdxT, typename OffT>
+bool launch_global_sort(const BwdCall& c, const IdxT* idx, const OffT* off, const BwdWs& w,
+                        const int32_t* bags, hipStream_t st) {
+  uint32_t *const k_x = w.keys_in, *const k_y = w.keys_out;
+  int32_t *const p_x = w.pos_in, *const p_y = w.pos_out;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w.partial);
+  const int npass = (bit_width_u64((uint64_t)c.total_rows) + DB - 1) / DB;
   TiledPass a{};
-  a.row_base = row_base, a.T = 1, a.B = 1, a.hist = hist, a.sentinel = sentinel, a.err = err;
-  a.bag_of = bag_of;
-  a.J = (int)dlrm::ceil_div(N, (int64_t)kTile);
+  a.row_base = c.row_base, a.T = 1, a.B = 1, a.hist = hist;
+  a.sentinel = (uint32_t)c.total_rows, a.err = c.err;
+  a.bag_of = bags;
+  a.J = (int)dlrm::ceil_div(c.N, (int64_t)kTile);
   a.global = 1;
-  a.n_all = N;
+  a.n_all = c.N;
   plan_scan_chunks(a);
   a.csum = hist + (size_t)a.J * (1 << DB);
   a.wide = a.J <= kWideScanMaxJ && (1 << DB) % 64 == 0 && dlrm::tuning(DLRM_TUNE_TBE_SORT) != 2;
@@ -862,58 +937,58 @@ bool launch_global_sort(const IdxT* idx, const OffT* off, const int64_t* row_bas
   return (npass & 1) == 1;
 }
 
-template <typename KeyT>
-struct BwdWs {
-  KeyT* keys_in;
-  KeyT* keys_out;
-  int32_t* pos_in;
-  int32_t* pos_out;
-  int32_t* bag_of;
-  float* partial;  // block partials; the sorts' digit histograms before the block kernel
-  size_t partial_words;
-  size_t total;
-};
-
-template <typename KeyT>
-BwdWs<KeyT> carve_bwd_ws(void* base, int64_t N, int64_t D, int end_bit) {
-  BwdWs<KeyT> w{};
-  WsCarver c(base);
-  w.keys_in = c.take<KeyT>(N);
-  w.keys_out = c.take<KeyT>(N);
-  w.pos_in = c.take<int32_t>(N);
-  w.pos_out = c.take<int32_t>(N);
-  w.bag_of = c.take<int32_t>(N);
-  (void)end_bit;
-  const size_t part = (size_t)2 * ((N + CH - 1) / CH) * D;
-  // global sort, 10-bit digits: per-tile counts + the scan's chunk sums
-  const size_t hist = (size_t)((N + kTile - 1) / kTile) * 1024 + (size_t)kMaxScanChunks * 1024;
-  w.partial_words = part > hist ? part : hist;
-  w.partial = c.take<float>(w.partial_words);
-  w.total = c.used + 256;
-  return w;
+// The argument checks every backward entry point shares, in one order.  The sort-only entry
+// takes no weights, gradient or presorted flag (with_update = false).
+int check_bwd_call(const BwdCall& c, bool with_update) {
+  DLRM_ARG((!with_update || (c.W && c.gout)) && c.row_base && (c.N == 0 || (c.idx && c.off)),
+           "%s: null pointer", c.name);
+  DLRM_ARG(!with_update || (c.presorted >= 0 && c.presorted <= DLRM_PRESORTED_ANY),
+           "%s: bad presorted %d", c.name, c.presorted);
+  DLRM_ARG(c.T > 0 && c.B > 0 && c.D > 0 && c.N >= 0 && c.total_rows > 0, "%s: bad sizes",
+           c.name);
+  DLRM_ARG(c.index_bits == 32 || c.index_bits == 64, "%s: index_bits must be 32 or 64", c.name);
+  DLRM_ARG(c.offset_bits == 32 || c.offset_bits == 64, "%s: offset_bits must be 32 or 64",
+           c.name);
+  DLRM_REQUIRE(c.N < (int64_t)INT32_MAX && (int64_t)c.T * c.B < (int64_t)INT32_MAX,
+               DLRM_ERR_UNSUPPORTED, "%s: more than 2^31 lookups/bags per call", c.name);
+  DLRM_ARG(!with_update || c.gbs >= (int64_t)c.T * c.D, "%s: grad_batch_stride < T*D", c.name);
+  DLRM_ARG(c.ws || c.N == 0, "%s: null workspace", c.name);
+  // 32-bit row keys: the sorts key on global rows (< 2^32 - 1 rows per call, e.g. 2^32
+  // rows of D = 16 fp32 is 275 GB, beyond one GPU's table budget; shard across calls)
+  DLRM_REQUIRE((uint64_t)c.total_rows < 0xFFFFFFFFull, DLRM_ERR_UNSUPPORTED,
+               "%s: %lld rows in one call (at most 2^32 - 2)", c.name, (long long)c.total_rows);
+  return DLRM_OK;
 }
 
-template <typename KeyT, typename IdxT, typename OffT>
-int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_base, int T, int B,
-               const void* idx, const void* off, int64_t N, int64_t total_rows, const float* psw,
-               const float* gout, int64_t gbs, float lr, const float* lr_dev, float eps, void* ws,
-               size_t ws_bytes, int64_t max_seg, int32_t* err, int presorted, LaunchRole* defer,
-               hipStream_t st, const char* name, bool sort_only = false,
-               const uint64_t* sr_state = nullptr) {
-  if (defer) {  // until proven fusable: nothing deferred
-    *defer = LaunchRole{};
-    defer->magic = kRoleMagic;
-  }
-  if (N == 0) return DLRM_OK;
-  const KeyT sentinel = (KeyT)total_rows;
-  const int end_bit = bit_width_u64((uint64_t)total_rows);
-  BwdWs<KeyT> w = carve_bwd_ws<KeyT>(ws, N, D, end_bit);
-  DLRM_REQUIRE(ws_bytes >= w.total, DLRM_ERR_WORKSPACE, "%s: workspace %zu < required %zu",
-               name, ws_bytes, w.total);
-  const bool per_table = presort_applies(sizeof(KeyT), max_seg, N);
+int carve_checked(const BwdCall& c, BwdWs& w) {
+  w = carve_bwd_ws(c.ws, c.N, c.D);
+  DLRM_REQUIRE(c.ws_bytes >= w.total, DLRM_ERR_WORKSPACE, "%s: workspace %zu < required %zu",
+               c.name, c.ws_bytes, w.total);
+  return DLRM_OK;
+}
+
+// Where the sort stage left the lookups, grouped by row.
+struct SortedRuns {
+  const uint32_t* keys;   // global rows, ascending; the sentinel where there is no update
+  const int32_t* pos;     // the sorted lookups' positions (their bags where the sort carried bags)
+  const int32_t* bag_of;  // each lookup's bag: in sorted order (bags_sorted) or by position
+  bool bags_sorted;
+};
+
+// The sort stage: this batch's (row, lookup) pairs sorted by row - already (presorted), or by
+// the per-table LDS sort, the tiled per-table sort or the device-wide sort.
+template <typename IdxT, typename OffT>
+int sort_stage(const BwdCall& c, const IdxT* idx, const OffT* off, const BwdWs& w,
+               SortedRuns& s) {
+  hipStream_t st = dlrm::as_stream(c.stream);
+  const int T = c.T;
+  const int64_t N = c.N;
+  const uint32_t sentinel = (uint32_t)c.total_rows;
+  const int end_bit = bit_width_u64((uint64_t)c.total_rows);
+  const bool per_table = presort_applies(c.max_seg, N);
   // large tables (> kSegCap lookups): the tiled per-table sort, its digit histograms in the
   // block kernel's partial buffer (free until the sort is done)
-  const int64_t tiles_j = dlrm::ceil_div(max_seg > 0 ? max_seg : 1, (int64_t)kTile);
+  const int64_t tiles_j = dlrm::ceil_div(c.max_seg > 0 ? c.max_seg : 1, (int64_t)kTile);
   const int tdb = tiled_digit_bits(end_bit);  // the device-wide sort (global keys)
   // the tiled sort passes over each table's OWN key bits (pass_view): 10-bit digits never
   // need more passes than 8-bit ones there, and only the tables that need them run them
@@ -921,204 +996,162 @@ int launch_bwd(int mode, float* W, float* mom, int64_t D, const int64_t* row_bas
   // per-tile counts + the scan's chunk sums (at most kMaxScanChunks per table)
   const int64_t sort_words = (int64_t)T * (tiles_j + kMaxScanChunks);
   const int tdb_t = sort_words * (1 << 10) <= part_space ? 10 : tdb;
-  const bool tiled = !per_table && sizeof(KeyT) == 4 && max_seg > kSegCap &&
-                     N < (int64_t)0x7fffffff && (int64_t)T * tiles_j < (int64_t)INT32_MAX &&
+  const bool tiled = !per_table && c.max_seg > kSegCap && N < (int64_t)0x7fffffff &&
+                     (int64_t)T * tiles_j < (int64_t)INT32_MAX &&
                      sort_words * (1 << tdb_t) <= part_space &&
                      dlrm::tuning(DLRM_TUNE_TBE_SORT) != 1;
   // the tiled and global sorts carry each lookup's bag (not its position) when no
   // per-sample weights need the position: the block kernel then reads bags in sorted order
-  const int32_t* bags = (!per_table && psw == nullptr) ? w.bag_of : nullptr;
-  if (presorted == DLRM_PRESORTED_ANY || (per_table && presorted)) {
+  const int32_t* bags = (!per_table && c.psw == nullptr) ? w.bag_of : nullptr;
+  // every sort but the device-wide one ends in (keys_out, pos_out); that one ping-pongs from
+  // (keys_in, pos_in) and ends there after an even number of passes
+  bool in_out = true;
+  if (c.presorted == DLRM_PRESORTED_ANY || (per_table && c.presorted)) {
     // this batch's sort already ran: inside dlrm_tbe_forward_presort (per-table), or in
-    // dlrm_tbe_backward_sort (any variant; the device-wide one ends in x or y by its parity)
-    if (!per_table && !tiled && ((end_bit + tdb - 1) / tdb) % 2 == 0) {
-      std::swap(w.keys_in, w.keys_out);
-      std::swap(w.pos_in, w.pos_out);
-    }
+    // dlrm_tbe_backward_sort (any variant; the device-wide one ends by its parity)
+    if (!per_table && !tiled) in_out = ((end_bit + tdb - 1) / tdb) % 2 == 1;
   } else if (per_table) {
     hipLaunchKernelGGL((tbe_bwd_segsort_kernel<IdxT, OffT>), dim3(T + 1), dim3(kSegThreads), 0,
-                       st, static_cast<const IdxT*>(idx), static_cast<const OffT*>(off), row_base,
-                       T, B, N, (uint32_t)sentinel, reinterpret_cast<uint32_t*>(w.keys_out),
-                       w.pos_out, w.bag_of, err);
-    DLRM_LAUNCH_CHECK(name);
+                       st, idx, off, c.row_base, T, c.B, N, sentinel, w.keys_out, w.pos_out,
+                       w.bag_of, c.err);
   } else if (tiled) {
-    const KeysArgs ka{row_base, T, B, N, (uint32_t)sentinel,
-                      reinterpret_cast<uint32_t*>(w.keys_out), w.pos_out, w.bag_of, err,
-                      keys_grid(T, B)};
-    auto* ko = reinterpret_cast<uint32_t*>(w.keys_out);
-    auto* ki = reinterpret_cast<uint32_t*>(w.keys_in);
-    auto* hist = reinterpret_cast<uint32_t*>(w.partial);
-    if (tdb_t == 10)
-      launch_tiled_sort<IdxT, OffT, 10>(static_cast<const IdxT*>(idx),
-                                        static_cast<const OffT*>(off), row_base, T, B,
-                                        (int)tiles_j, end_bit, ki, w.pos_in, ko, w.pos_out, hist,
-                                        (uint32_t)sentinel, err, (int)sizeof(OffT) * 8, bags, ka,
-                                        st);
-    else
-      launch_tiled_sort<IdxT, OffT, 8>(static_cast<const IdxT*>(idx),
-                                       static_cast<const OffT*>(off), row_base, T, B,
-                                       (int)tiles_j, end_bit, ki, w.pos_in, ko, w.pos_out, hist,
-                                       (uint32_t)sentinel, err, (int)sizeof(OffT) * 8, bags, ka,
-                                       st);
-    DLRM_LAUNCH_CHECK(name);
+    for_digit_bits(tdb_t, [&](auto db) {
+      launch_tiled_sort<decltype(db)::value>(c, idx, off, w, (int)tiles_j, bags, st);
+    });
   } else {
-    hipLaunchKernelGGL((tbe_bwd_keys_kernel<IdxT, OffT, KeyT, true>), dim3(keys_grid(T, B)),
-                       dim3(256), 0, st, static_cast<const IdxT*>(idx),
-                       static_cast<const OffT*>(off), row_base, T, B, N, sentinel, w.keys_in,
-                       w.pos_in, w.bag_of, err);
-    DLRM_LAUNCH_CHECK(name);
-    auto* ki = reinterpret_cast<uint32_t*>(w.keys_in);
-    auto* ko = reinterpret_cast<uint32_t*>(w.keys_out);
-    auto* hist = reinterpret_cast<uint32_t*>(w.partial);
-    const bool in_y =
-        tdb == 10 ? launch_global_sort<IdxT, OffT, 10>(static_cast<const IdxT*>(idx),
-                                                       static_cast<const OffT*>(off), row_base, N,
-                                                       end_bit, ki, w.pos_in, ko, w.pos_out, hist,
-                                                       (uint32_t)sentinel, err, bags, st)
-                  : launch_global_sort<IdxT, OffT, 8>(static_cast<const IdxT*>(idx),
-                                                      static_cast<const OffT*>(off), row_base, N,
-                                                      end_bit, ki, w.pos_in, ko, w.pos_out, hist,
-                                                      (uint32_t)sentinel, err, bags, st);
-    DLRM_LAUNCH_CHECK(name);
-    if (!in_y) {  // an even pass count left the sorted pairs in the input buffers
-      std::swap(w.keys_in, w.keys_out);
-      std::swap(w.pos_in, w.pos_out);
-    }
+    hipLaunchKernelGGL((tbe_bwd_keys_kernel<IdxT, OffT, uint32_t, true>), dim3(keys_grid(T, c.B)),
+                       dim3(256), 0, st, idx, off, c.row_base, T, c.B, N, sentinel, w.keys_in,
+                       w.pos_in, w.bag_of, c.err);
+    DLRM_LAUNCH_CHECK(c.name);
+    in_out = for_digit_bits(tdb, [&](auto db) {
+      return launch_global_sort<decltype(db)::value>(c, idx, off, w, bags, st);
+    });
   }
-
-  if (sort_only) return DLRM_OK;
-
-  const bool f16_rows = mode == MODE_SGD_F16 || mode == MODE_SGD_F16_SR;
-  // (element-wise Adagrad: the state rows are read and written like the weight rows)
-  const bool vec4 = (D % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(W) & (f16_rows ? 7 : 15)) == 0) &&
-                    (mode != MODE_ADAGRAD_ELEM || (reinterpret_cast<uintptr_t>(mom) & 15) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(gout) & 15) == 0) && (gbs % 4 == 0);
-  const int64_t nchunks = vec4 ? D / 4 : D;
-  int lpb = 1;
-  while (lpb < nchunks && lpb < 64) lpb <<= 1;
-  const int64_t maxv = dlrm::ceil_div(nchunks, lpb);
-  DLRM_REQUIRE(maxv <= 8, DLRM_ERR_UNSUPPORTED, "%s: D=%lld too large", name, (long long)D);
-  const int gpw = 64 / lpb;
-  int ch = N >= kLongChN ? kLongCH : CH;
-  const int64_t tch = dlrm::tuning(DLRM_TUNE_TBE_BLOCK);  // (sweeps / coverage tests)
-  if (tch == CH || tch == kLongCH) ch = (int)tch;
-  const int64_t nblocks = dlrm::ceil_div(N, (int64_t)ch);
-  int64_t blocks = dlrm::ceil_div(dlrm::ceil_div(nblocks, gpw), 4);
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  // the lean passes (4 gradient rows in flight per lane group at <= 128 VGPRs: twice the
-  // resident waves of the 16-in-flight kernels, C1 block pass 100 -> ~65 us) wherever they
-  // apply - deferred into later launches, or launched here
-  if (sizeof(KeyT) == 4 && vec4 && maxv == 1 && (per_table || bags) &&
-      tbe_role_fusable(mode, lpb, psw, (int64_t)B * gbs) &&
-      (defer || dlrm::tuning(DLRM_TUNE_TBE_LEAN) != 1)) {
-    LaunchRole local{};
-    LaunchRole& r = defer ? *defer : local;
-    r.W = W, r.mom = mom, r.psw = psw, r.gout = gout, r.partial = w.partial;
-    r.keys = reinterpret_cast<const uint32_t*>(w.keys_out);
-    r.pos = w.pos_out;
-    r.bag_of = per_table ? w.bag_of : w.pos_out;
-    r.D = D, r.gbs = gbs, r.N = N, r.lr = lr, r.lr_dev = lr_dev, r.eps = eps;
-    r.sentinel = (uint32_t)sentinel;
-    r.B = B, r.ch = ch, r.mode = mode, r.lpb = lpb;
-    // a multiple of 8 workgroups keeps the co-launched GEMM tiles' XCD remap aligned
-    r.blocks = (int32_t)(dlrm::ceil_div(blocks, (int64_t)8) * 8);
-    r.kind = kRoleUpdate;
-    r.magic = kRoleMagic;
-    if (defer) return DLRM_OK;
-    hipLaunchKernelGGL(tbe_update_pass_kernel<1>, dim3(r.blocks), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(tbe_update_pass_kernel<2>, dim3(r.blocks), dim3(256), 0, st, r);
-    DLRM_LAUNCH_CHECK(name);
-    return DLRM_OK;
-  }
-#define LAUNCH2(LPB, VW, MV, MODE)                                                             \
-  do {                                                                                         \
-    if (per_table || bags)                                                                     \
-      hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, true>), dim3(blocks),  \
-                         dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out,                \
-                         per_table ? w.bag_of : w.pos_out, psw, gout, gbs, N, lr, eps,         \
-                         sentinel, w.partial, ch, lr_dev, sr_state);                           \
-    else                                                                                       \
-      hipLaunchKernelGGL((tbe_bwd_block_kernel<LPB, VW, MV, KeyT, MODE, false>), dim3(blocks), \
-                         dim3(256), 0, st, W, mom, D, B, w.keys_out, w.pos_out, w.bag_of, psw, \
-                         gout, gbs, N, lr, eps, sentinel, w.partial, ch, lr_dev, sr_state);    \
-    hipLaunchKernelGGL((tbe_bwd_combine_kernel<LPB, VW, MV, KeyT, MODE>), dim3(blocks),        \
-                       dim3(256), 0, st, W, mom, D, w.keys_out, N, lr, eps, sentinel,          \
-                       w.partial, ch, lr_dev, sr_state);                                       \
-  } while (0)
-#define BY_LPB(VW, MODE)                             \
-  switch (lpb) {                                     \
-    case 1: LAUNCH2(1, VW, 1, MODE); break;          \
-    case 2: LAUNCH2(2, VW, 1, MODE); break;          \
-    case 4: LAUNCH2(4, VW, 1, MODE); break;          \
-    case 8: LAUNCH2(8, VW, 1, MODE); break;          \
-    case 16: LAUNCH2(16, VW, 1, MODE); break;        \
-    case 32: LAUNCH2(32, VW, 1, MODE); break;        \
-    default:                                         \
-      if (maxv == 1) LAUNCH2(64, VW, 1, MODE);       \
-      else if (maxv == 2) LAUNCH2(64, VW, 2, MODE);  \
-      else if (maxv <= 4) LAUNCH2(64, VW, 4, MODE);  \
-      else LAUNCH2(64, VW, 8, MODE);                 \
-  }
-#define BY_MODE(VW)                    \
-  if (mode == MODE_SGD) {              \
-    BY_LPB(VW, MODE_SGD)               \
-  } else if (mode == MODE_ADAGRAD) {   \
-    BY_LPB(VW, MODE_ADAGRAD)           \
-  } else if (mode == MODE_SGD_F16) {   \
-    BY_LPB(VW, MODE_SGD_F16)           \
-  } else if (mode == MODE_SGD_F16_SR) {\
-    BY_LPB(VW, MODE_SGD_F16_SR)        \
-  } else if (mode == MODE_ADAGRAD_ELEM) {\
-    BY_LPB(VW, MODE_ADAGRAD_ELEM)      \
-  } else {                             \
-    BY_LPB(VW, MODE_DENSE)             \
-  }
-  if (vec4) {
-    BY_MODE(4)
-  } else {
-    BY_MODE(1)
-  }
-#undef BY_MODE
-#undef BY_LPB
-#undef LAUNCH2
-  DLRM_LAUNCH_CHECK(name);
+  DLRM_LAUNCH_CHECK(c.name);
+  s.keys = in_out ? w.keys_out : w.keys_in;
+  s.pos = in_out ? w.pos_out : w.pos_in;
+  s.bags_sorted = per_table || bags;
+  s.bag_of = per_table || !bags ? w.bag_of : s.pos;
   return DLRM_OK;
 }
 
-int bwd_dispatch(int mode, float* W, float* mom, int64_t D, const int64_t* row_base, int T,
-                 int B, const void* idx, int ib, const void* off, int ob, int64_t N,
-                 int64_t total_rows, const float* psw, const float* gout, int64_t gbs, float lr,
-                 float eps, void* ws, size_t ws_bytes, int64_t max_seg, int32_t* err,
-                 int presorted, LaunchRole* defer, dlrm_stream_t stream, const char* name,
-                 bool sort_only = false, const float* lr_dev = nullptr,
-                 const uint64_t* sr_state = nullptr) {
-  DLRM_ARG(((W && gout) || sort_only) && row_base && (N == 0 || (idx && off)),
-           "%s: null pointer", name);
-  DLRM_ARG(presorted >= 0 && presorted <= DLRM_PRESORTED_ANY, "%s: bad presorted %d", name,
-           presorted);
-  DLRM_ARG(T > 0 && B > 0 && D > 0 && N >= 0 && total_rows > 0, "%s: bad sizes", name);
-  DLRM_ARG(ib == 32 || ib == 64, "%s: index_bits must be 32 or 64", name);
-  DLRM_ARG(ob == 32 || ob == 64, "%s: offset_bits must be 32 or 64", name);
-  DLRM_REQUIRE(N < (int64_t)INT32_MAX && (int64_t)T * B < (int64_t)INT32_MAX,
-               DLRM_ERR_UNSUPPORTED, "%s: more than 2^31 lookups/bags per call", name);
-  DLRM_ARG(gbs >= (int64_t)T * D, "%s: grad_batch_stride < T*D", name);
-  DLRM_ARG(ws || N == 0, "%s: null workspace", name);
-  hipStream_t st = dlrm::as_stream(stream);
-  // 32-bit row keys: the sorts key on global rows (< 2^32 - 1 rows per call, e.g. 2^32
-  // rows of D = 16 fp32 is 275 GB, beyond one GPU's table budget; shard across calls)
-  DLRM_REQUIRE((uint64_t)total_rows < 0xFFFFFFFFull, DLRM_ERR_UNSUPPORTED,
-               "%s: %lld rows in one call (at most 2^32 - 2)", name, (long long)total_rows);
-#define BWD(K, I, O)                                                                     \
-  return launch_bwd<K, I, O>(mode, W, mom, D, row_base, T, B, idx, off, N, total_rows, psw, \
-                             gout, gbs, lr, lr_dev, eps, ws, ws_bytes, max_seg, err, presorted, \
-                             defer, st, name, sort_only, sr_state)
-  if (ib == 32 && ob == 32) BWD(uint32_t, int32_t, int32_t);
-  if (ib == 32 && ob == 64) BWD(uint32_t, int32_t, int64_t);
-  if (ib == 64 && ob == 32) BWD(uint32_t, int64_t, int32_t);
-  BWD(uint32_t, int64_t, int64_t);
-#undef BWD
+int run_sort(const BwdCall& c, const BwdWs& w, SortedRuns& s) {
+  return for_csr_widths(c.index_bits, c.offset_bits, [&](auto i, auto o) {
+    return sort_stage(c, i.ptr(c.idx), o.ptr(c.off), w, s);
+  });
+}
+
+// The update's launch geometry.  It depends on the call alone, so it is planned (and a D
+// the kernels do not cover refused) before the sort has enqueued anything.
+struct UpdateGeom {
+  bool vec4;
+  LaneGeom lanes;
+  int ch;          // sorted lookups per block
+  int64_t blocks;  // workgroups of the block pass and of the combine pass
+};
+
+int plan_update(const BwdCall& c, UpdateGeom& u) {
+  const bool f16_rows = c.mode == MODE_SGD_F16 || c.mode == MODE_SGD_F16_SR;
+  // (element-wise Adagrad: the state rows are read and written like the weight rows)
+  u.vec4 = (c.D % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.W) & (f16_rows ? 7 : 15)) == 0) &&
+           (c.mode != MODE_ADAGRAD_ELEM || (reinterpret_cast<uintptr_t>(c.mom) & 15) == 0) &&
+           ((reinterpret_cast<uintptr_t>(c.gout) & 15) == 0) && (c.gbs % 4 == 0);
+  u.lanes = lane_geom(u.vec4 ? c.D / 4 : c.D);
+  DLRM_REQUIRE(u.lanes.maxv <= 8, DLRM_ERR_UNSUPPORTED, "%s: D=%lld too large", c.name,
+               (long long)c.D);
+  u.ch = c.N >= kLongChN ? kLongCH : CH;
+  const int64_t tch = dlrm::tuning(DLRM_TUNE_TBE_BLOCK);  // (sweeps / coverage tests)
+  if (tch == CH || tch == kLongCH) u.ch = (int)tch;
+  u.blocks = lane_blocks(dlrm::ceil_div(c.N, (int64_t)u.ch), u.lanes.lpb, 4);
+  return DLRM_OK;
+}
+
+// f(int_tag<MODE>): the update mode as a template argument.
+template <class F>
+void for_mode(int mode, F&& f) {
+  switch (mode) {
+    case MODE_SGD: return f(int_tag<MODE_SGD>{});
+    case MODE_ADAGRAD: return f(int_tag<MODE_ADAGRAD>{});
+    case MODE_SGD_F16: return f(int_tag<MODE_SGD_F16>{});
+    case MODE_SGD_F16_SR: return f(int_tag<MODE_SGD_F16_SR>{});
+    case MODE_ADAGRAD_ELEM: return f(int_tag<MODE_ADAGRAD_ELEM>{});
+    default: return f(int_tag<MODE_DENSE>{});
+  }
+}
+
+// The update stage: the block pass and the combine pass over the sorted lookups.
+int update_stage(const BwdCall& c, const UpdateGeom& u, const SortedRuns& s, float* partial) {
+  hipStream_t st = dlrm::as_stream(c.stream);
+  const uint32_t sentinel = (uint32_t)c.total_rows;
+  const int lpb = u.lanes.lpb;
+  // the lean passes (4 gradient rows in flight per lane group at <= 128 VGPRs: twice the
+  // resident waves of the 16-in-flight kernels, C1 block pass 100 -> ~65 us) wherever they
+  // apply - deferred into later launches, or launched here
+  if (u.vec4 && u.lanes.maxv == 1 && s.bags_sorted &&
+      tbe_role_fusable(c.mode, lpb, c.psw, (int64_t)c.B * c.gbs) &&
+      (c.role || dlrm::tuning(DLRM_TUNE_TBE_LEAN) != 1)) {
+    LaunchRole local{};
+    LaunchRole& r = c.role ? *c.role : local;
+    r.W = c.W, r.mom = c.mom, r.psw = c.psw, r.gout = c.gout, r.partial = partial;
+    r.keys = s.keys, r.pos = s.pos, r.bag_of = s.bag_of;
+    r.D = c.D, r.gbs = c.gbs, r.N = c.N, r.lr = c.lr, r.lr_dev = c.lr_dev, r.eps = c.eps;
+    r.sentinel = sentinel;
+    r.B = c.B, r.ch = u.ch, r.mode = c.mode, r.lpb = lpb;
+    // a multiple of 8 workgroups keeps the co-launched GEMM tiles' XCD remap aligned
+    r.blocks = (int32_t)(dlrm::ceil_div(u.blocks, (int64_t)8) * 8);
+    r.kind = kRoleUpdate;
+    r.magic = kRoleMagic;
+    if (c.role) return DLRM_OK;
+    hipLaunchKernelGGL(tbe_update_pass_kernel<1>, dim3(r.blocks), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(tbe_update_pass_kernel<2>, dim3(r.blocks), dim3(256), 0, st, r);
+    DLRM_LAUNCH_CHECK(c.name);
+    return DLRM_OK;
+  }
+  for_row_width(u.vec4, [&](auto vw) {
+    for_mode(c.mode, [&](auto mode) {
+      for_lanes<1, 8>(u.lanes, [&](auto lanes, auto mv) {
+        constexpr int LPB = decltype(lanes)::value, VW = decltype(vw)::value;
+        constexpr int MV = decltype(mv)::value, MODE = decltype(mode)::value;
+        const auto block = s.bags_sorted ? tbe_bwd_block_kernel<LPB, VW, MV, uint32_t, MODE, true>
+                                         : tbe_bwd_block_kernel<LPB, VW, MV, uint32_t, MODE, false>;
+        hipLaunchKernelGGL(block, dim3(u.blocks), dim3(256), 0, st, c.W, c.mom, c.D, c.B, s.keys,
+                           s.pos, s.bag_of, c.psw, c.gout, c.gbs, c.N, c.lr, c.eps, sentinel,
+                           partial, u.ch, c.lr_dev, c.sr_state);
+        hipLaunchKernelGGL((tbe_bwd_combine_kernel<LPB, VW, MV, uint32_t, MODE>), dim3(u.blocks),
+                           dim3(256), 0, st, c.W, c.mom, c.D, s.keys, c.N, c.lr, c.eps, sentinel,
+                           partial, u.ch, c.lr_dev, c.sr_state);
+      });
+    });
+  });
+  DLRM_LAUNCH_CHECK(c.name);
+  return DLRM_OK;
+}
+
+int bwd_dispatch(const BwdCall& c) {
+  if (c.role) {  // until proven fusable: nothing deferred (the one place a role starts)
+    *c.role = LaunchRole{};
+    c.role->magic = kRoleMagic;
+  }
+  if (const int rc = check_bwd_call(c, true)) return rc;
+  if (c.N == 0) return DLRM_OK;
+  BwdWs w{};
+  if (const int rc = carve_checked(c, w)) return rc;
+  UpdateGeom u{};
+  if (const int rc = plan_update(c, u)) return rc;
+  SortedRuns s{};
+  if (const int rc = run_sort(c, w, s)) return rc;
+  return update_stage(c, u, s, w.partial);
+}
+
+// The deferred entries' own checks; their mode argument is 0 (sgd) | 1 (rowwise adagrad).
+int bwd_defer(BwdCall& c, int32_t mode, dlrm_launch_role* role) {
+  DLRM_ARG(role, "%s: null role", c.name);
+  DLRM_ARG(mode == 0 || mode == 1, "%s: mode must be 0 (sgd) or 1 (rowwise adagrad)", c.name);
+  DLRM_ARG(mode == 0 || c.mom, "%s: rowwise adagrad needs momentum", c.name);
+  c.mode = mode == 0 ? MODE_SGD : MODE_ADAGRAD;
+  if (mode == 0) c.mom = nullptr;
+  c.role = reinterpret_cast<LaunchRole*>(role);
+  return bwd_dispatch(c);
 }
 
 }  // namespace
@@ -1127,8 +1160,8 @@ extern "C" size_t dlrm_tbe_backward_workspace_size(int64_t num_lookups, int64_t 
                                                    int64_t D) {
   if (num_lookups <= 0) return 256;
   if (D < 1) D = 1;
-  const int end_bit = bit_width_u64((uint64_t)(total_rows > 0 ? total_rows : 1));
-  return carve_bwd_ws<uint32_t>(nullptr, num_lookups, D, end_bit).total;
+  (void)total_rows;
+  return carve_bwd_ws(nullptr, num_lookups, D).total;
 }
 
 extern "C" int dlrm_tbe_backward_sgd(float* weights, int64_t D, const int64_t* row_base,
@@ -1140,11 +1173,15 @@ extern "C" int dlrm_tbe_backward_sgd(float* weights, int64_t D, const int64_t* r
                                      int64_t max_lookups_per_table, void* workspace,
                                      size_t workspace_bytes, int32_t* error_flag,
                                      int32_t presorted, dlrm_stream_t stream) {
-  return bwd_dispatch(MODE_SGD, weights, nullptr, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
-                      grad_out, grad_batch_stride, lr, 0.f, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_sgd");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sgd", c.mode = MODE_SGD, c.W = weights;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr = lr;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_sgd_dev(float* weights, int64_t D, const int64_t* row_base,
@@ -1158,11 +1195,15 @@ extern "C" int dlrm_tbe_backward_sgd_dev(float* weights, int64_t D, const int64_
                                          int32_t* error_flag, int32_t presorted,
                                          dlrm_stream_t stream) {
   DLRM_ARG(lr_dev, "dlrm_tbe_backward_sgd_dev: null lr_dev");
-  return bwd_dispatch(MODE_SGD, weights, nullptr, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
-                      grad_out, grad_batch_stride, 0.f, 0.f, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_sgd_dev", false, lr_dev);
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sgd_dev", c.mode = MODE_SGD, c.W = weights;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr_dev = lr_dev;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_sgd_f16(void* weights, int64_t D, const int64_t* row_base,
@@ -1175,11 +1216,16 @@ extern "C" int dlrm_tbe_backward_sgd_f16(void* weights, int64_t D, const int64_t
                                          void* workspace, size_t workspace_bytes,
                                          int32_t* error_flag, int32_t presorted,
                                          dlrm_stream_t stream) {
-  return bwd_dispatch(MODE_SGD_F16, static_cast<float*>(weights), nullptr, D, row_base, T, B,
-                      indices, index_bits, offsets, offset_bits, num_lookups, total_rows,
-                      per_sample_weights, grad_out, grad_batch_stride, lr, 0.f, workspace,
-                      workspace_bytes, max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_sgd_f16");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sgd_f16", c.mode = MODE_SGD_F16;
+  c.W = static_cast<float*>(weights);
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr = lr;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int64_t* row_base,
@@ -1193,11 +1239,16 @@ extern "C" int dlrm_tbe_backward_sgd_f16_dev(void* weights, int64_t D, const int
                                              int32_t* error_flag, int32_t presorted,
                                              dlrm_stream_t stream) {
   DLRM_ARG(lr_dev, "dlrm_tbe_backward_sgd_f16_dev: null lr_dev");
-  return bwd_dispatch(MODE_SGD_F16, static_cast<float*>(weights), nullptr, D, row_base, T, B,
-                      indices, index_bits, offsets, offset_bits, num_lookups, total_rows,
-                      per_sample_weights, grad_out, grad_batch_stride, 0.f, 0.f, workspace,
-                      workspace_bytes, max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_sgd_f16_dev", false, lr_dev);
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sgd_f16_dev", c.mode = MODE_SGD_F16;
+  c.W = static_cast<float*>(weights);
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr_dev = lr_dev;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 // ABI v16: the fp16 update with the store rounded stochastically; the stream's (seed, step)
@@ -1213,14 +1264,19 @@ extern "C" int dlrm_tbe_backward_sgd_f16_sr(void* weights, int64_t D, const int6
                                             int64_t max_lookups_per_table, void* workspace,
                                             size_t workspace_bytes, int32_t* error_flag,
                                             int32_t presorted, dlrm_stream_t stream) {
-  const char* name = "dlrm_tbe_backward_sgd_f16_sr";
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sgd_f16_sr", c.mode = MODE_SGD_F16_SR;
   DLRM_ARG(sr_state && (reinterpret_cast<uintptr_t>(sr_state) & 7) == 0,
-           "%s: sr_state must be an 8-byte aligned device pointer", name);
-  return bwd_dispatch(MODE_SGD_F16_SR, static_cast<float*>(weights), nullptr, D, row_base, T, B,
-                      indices, index_bits, offsets, offset_bits, num_lookups, total_rows,
-                      per_sample_weights, grad_out, grad_batch_stride, lr_dev ? 0.f : lr, 0.f,
-                      workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted,
-                      nullptr, stream, name, false, lr_dev, sr_state);
+           "%s: sr_state must be an 8-byte aligned device pointer", c.name);
+  c.W = static_cast<float*>(weights);
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride;
+  c.lr = lr_dev ? 0.f : lr, c.lr_dev = lr_dev, c.sr_state = sr_state;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_rowwise_adagrad(
@@ -1231,11 +1287,16 @@ extern "C" int dlrm_tbe_backward_rowwise_adagrad(
     int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes, int32_t* error_flag,
     int32_t presorted, dlrm_stream_t stream) {
   DLRM_ARG(momentum, "dlrm_tbe_backward_rowwise_adagrad: null momentum");
-  return bwd_dispatch(MODE_ADAGRAD, weights, momentum, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
-                      grad_out, grad_batch_stride, lr, eps, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_rowwise_adagrad");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_rowwise_adagrad", c.mode = MODE_ADAGRAD;
+  c.W = weights, c.mom = momentum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr = lr, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_rowwise_adagrad_dev(
@@ -1245,13 +1306,17 @@ extern "C" int dlrm_tbe_backward_rowwise_adagrad_dev(
     const float* grad_out, int64_t grad_batch_stride, const float* lr_dev, float eps,
     int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes, int32_t* error_flag,
     int32_t presorted, dlrm_stream_t stream) {
-  const char* name = "dlrm_tbe_backward_rowwise_adagrad_dev";
-  DLRM_ARG(momentum && lr_dev, "%s: null momentum or lr_dev", name);
-  return bwd_dispatch(MODE_ADAGRAD, weights, momentum, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
-                      grad_out, grad_batch_stride, 0.f, eps, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, presorted, nullptr, stream, name, false,
-                      lr_dev);
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_rowwise_adagrad_dev", c.mode = MODE_ADAGRAD;
+  DLRM_ARG(momentum && lr_dev, "%s: null momentum or lr_dev", c.name);
+  c.W = weights, c.mom = momentum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr_dev = lr_dev, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 // ABI v19: element-wise Adagrad (torch.optim.Adagrad, dlrm_s_pytorch.py:1642) on the rows
@@ -1264,11 +1329,17 @@ extern "C" int dlrm_tbe_backward_adagrad(
     int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes, int32_t* error_flag,
     int32_t presorted, dlrm_stream_t stream) {
   DLRM_ARG(state_sum, "dlrm_tbe_backward_adagrad: null state_sum");
-  return bwd_dispatch(MODE_ADAGRAD_ELEM, weights, state_sum, D, row_base, T, B, indices,
-                      index_bits, offsets, offset_bits, num_lookups, total_rows,
-                      per_sample_weights, grad_out, grad_batch_stride, lr_dev ? 0.f : lr, eps,
-                      workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted,
-                      nullptr, stream, "dlrm_tbe_backward_adagrad", false, lr_dev);
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_adagrad", c.mode = MODE_ADAGRAD_ELEM;
+  c.W = weights, c.mom = state_sum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride;
+  c.lr = lr_dev ? 0.f : lr, c.lr_dev = lr_dev, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 extern "C" int dlrm_tbe_backward_dense(float* grad_weights, int64_t D, const int64_t* row_base,
@@ -1280,15 +1351,20 @@ extern "C" int dlrm_tbe_backward_dense(float* grad_weights, int64_t D, const int
                                        int64_t max_lookups_per_table, void* workspace,
                                        size_t workspace_bytes, int32_t* error_flag,
                                        int32_t presorted, dlrm_stream_t stream) {
-  return bwd_dispatch(MODE_DENSE, grad_weights, nullptr, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights,
-                      grad_out, grad_batch_stride, 0.f, 0.f, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, presorted, nullptr, stream,
-                      "dlrm_tbe_backward_dense");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_dense", c.mode = MODE_DENSE, c.W = grad_weights;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
 }
 
 static_assert(sizeof(LaunchRole) <= sizeof(dlrm_launch_role), "dlrm_launch_role too small");
 
+// The sort stage alone: no update, so no weights, gradient, mode or D refusal.
 extern "C" int dlrm_tbe_backward_sort(int64_t D, const int64_t* row_base, int32_t T, int32_t B,
                                       const void* indices, int32_t index_bits,
                                       const void* offsets, int32_t offset_bits,
@@ -1297,35 +1373,20 @@ extern "C" int dlrm_tbe_backward_sort(int64_t D, const int64_t* row_base, int32_
                                       int64_t max_lookups_per_table, void* workspace,
                                       size_t workspace_bytes, int32_t* error_flag,
                                       dlrm_stream_t stream) {
-  return bwd_dispatch(MODE_SGD, nullptr, nullptr, D, row_base, T, B, indices, index_bits,
-                      offsets, offset_bits, num_lookups, total_rows, per_sample_weights, nullptr,
-                      (int64_t)T * D, 0.f, 0.f, workspace, workspace_bytes,
-                      max_lookups_per_table, error_flag, 0, nullptr, stream,
-                      "dlrm_tbe_backward_sort", true);
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_sort";
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.stream = stream;
+  if (const int rc = check_bwd_call(c, false)) return rc;
+  if (c.N == 0) return DLRM_OK;
+  BwdWs w{};
+  if (const int rc = carve_checked(c, w)) return rc;
+  SortedRuns s{};
+  return run_sort(c, w, s);
 }
-
-namespace {
-int backward_defer(
-    int32_t mode, float* weights, float* momentum, int64_t D, const int64_t* row_base,
-    int32_t T, int32_t B, const void* indices, int32_t index_bits, const void* offsets,
-    int32_t offset_bits, int64_t num_lookups, int64_t total_rows,
-    const float* per_sample_weights, const float* grad_out, int64_t grad_batch_stride, float lr,
-    const float* lr_dev, float eps, int64_t max_lookups_per_table, void* workspace,
-    size_t workspace_bytes, int32_t* error_flag, int32_t presorted, dlrm_launch_role* role,
-    dlrm_stream_t stream, const char* name) {
-  DLRM_ARG(role, "%s: null role", name);
-  DLRM_ARG(mode == 0 || mode == 1, "%s: mode must be 0 (sgd) or 1 (rowwise adagrad)", name);
-  DLRM_ARG(mode == 0 || momentum, "%s: rowwise adagrad needs momentum", name);
-  auto* r = reinterpret_cast<LaunchRole*>(role);
-  *r = LaunchRole{};
-  r->magic = kRoleMagic;
-  return bwd_dispatch(mode == 0 ? MODE_SGD : MODE_ADAGRAD, weights, mode == 0 ? nullptr : momentum,
-                      D, row_base, T, B, indices, index_bits, offsets, offset_bits, num_lookups,
-                      total_rows, per_sample_weights, grad_out, grad_batch_stride, lr, eps,
-                      workspace, workspace_bytes, max_lookups_per_table, error_flag, presorted, r,
-                      stream, name, false, lr_dev);
-}
-}  // namespace
 
 extern "C" int dlrm_tbe_backward_defer(
     int32_t mode, float* weights, float* momentum, int64_t D, const int64_t* row_base,
@@ -1334,11 +1395,15 @@ extern "C" int dlrm_tbe_backward_defer(
     const float* per_sample_weights, const float* grad_out, int64_t grad_batch_stride, float lr,
     float eps, int64_t max_lookups_per_table, void* workspace, size_t workspace_bytes,
     int32_t* error_flag, int32_t presorted, dlrm_launch_role* role, dlrm_stream_t stream) {
-  return backward_defer(mode, weights, momentum, D, row_base, T, B, indices, index_bits, offsets,
-                        offset_bits, num_lookups, total_rows, per_sample_weights, grad_out,
-                        grad_batch_stride, lr, nullptr, eps, max_lookups_per_table, workspace,
-                        workspace_bytes, error_flag, presorted, role, stream,
-                        "dlrm_tbe_backward_defer");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_defer", c.W = weights, c.mom = momentum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr = lr, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_defer(c, mode, role);
 }
 
 extern "C" int dlrm_tbe_backward_defer_dev(
@@ -1350,83 +1415,21 @@ extern "C" int dlrm_tbe_backward_defer_dev(
     size_t workspace_bytes, int32_t* error_flag, int32_t presorted, dlrm_launch_role* role,
     dlrm_stream_t stream) {
   DLRM_ARG(lr_dev, "dlrm_tbe_backward_defer_dev: null lr_dev");
-  return backward_defer(mode, weights, momentum, D, row_base, T, B, indices, index_bits, offsets,
-                        offset_bits, num_lookups, total_rows, per_sample_weights, grad_out,
-                        grad_batch_stride, 0.f, lr_dev, eps, max_lookups_per_table, workspace,
-                        workspace_bytes, error_flag, presorted, role, stream,
-                        "dlrm_tbe_backward_defer_dev");
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_defer_dev", c.W = weights, c.mom = momentum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride, c.lr_dev = lr_dev, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_defer(c, mode, role);
 }
 
 extern "C" int32_t dlrm_role_blocks(const dlrm_launch_role* role) {
   const auto* r = reinterpret_cast<const LaunchRole*>(role);
   return r && r->magic == kRoleMagic ? r->blocks : 0;
 }
-
-namespace {
-
-template <typename IdxT, typename OffT>
-int launch_fwd_presort(const float* W, int64_t D, const int64_t* row_base, int T, int B,
-                       const void* idx, const void* off, const float* psw, float* out,
-                       int64_t out_bs, int64_t N, int64_t total_rows, void* ws, size_t ws_bytes,
-                       int32_t* err, const MlpChain& mc, int mlp_blocks, bool sort,
-                       hipStream_t st) {
-  const char* name = "dlrm_tbe_forward_presort";
-  BwdWs<uint32_t> w{};
-  if (sort) {
-    const int end_bit = bit_width_u64((uint64_t)total_rows);
-    w = carve_bwd_ws<uint32_t>(ws, N, D, end_bit);
-    DLRM_REQUIRE(ws_bytes >= w.total, DLRM_ERR_WORKSPACE, "%s: workspace %zu < required %zu",
-                 name, ws_bytes, w.total);
-  }
-  const int nsort = sort ? T + 1 : 0;
-  const bool vec4 = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(W) & 15) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (out_bs % 4 == 0);
-  const int64_t nchunks = vec4 ? D / 4 : D;
-  int lpb = 1;
-  while (lpb < nchunks && lpb < 64) lpb <<= 1;
-  const int64_t maxv = dlrm::ceil_div(nchunks, lpb);
-  DLRM_REQUIRE(maxv <= 8, DLRM_ERR_UNSUPPORTED, "%s: D=%lld too large", name, (long long)D);
-  const int64_t nbags = (int64_t)T * B;
-  const int gpw = 64 / lpb;
-  int64_t gblocks = dlrm::ceil_div(dlrm::ceil_div(nbags, gpw), kPreThreads / 64);
-  if (gblocks > 8192) gblocks = 8192;
-  if (gblocks < 1) gblocks = 1;
-  if (!out) gblocks = 0;  // the lookup is fused into its consumer (interaction gather)
-  const dim3 grid((unsigned)(nsort + mlp_blocks + gblocks)), block(kPreThreads);
-  const IdxT* ip = static_cast<const IdxT*>(idx);
-  const OffT* op = static_cast<const OffT*>(off);
-  const uint32_t sentinel = (uint32_t)total_rows;
-#define PRE(LPB, VW, MV)                                                                         \
-  hipLaunchKernelGGL((tbe_fwd_presort_kernel<LPB, VW, MV, IdxT, OffT>), grid, block, 0, st, W, D, \
-                     row_base, T, B, ip, op, psw, out, out_bs, err, N, sentinel,                  \
-                     reinterpret_cast<uint32_t*>(w.keys_out), w.pos_out, w.bag_of, mc,       \
-                     mlp_blocks, nsort)
-#define PRE_LPB(VW)                        \
-  switch (lpb) {                           \
-    case 1: PRE(1, VW, 1); break;          \
-    case 2: PRE(2, VW, 1); break;          \
-    case 4: PRE(4, VW, 1); break;          \
-    case 8: PRE(8, VW, 1); break;          \
-    case 16: PRE(16, VW, 1); break;        \
-    case 32: PRE(32, VW, 1); break;        \
-    default:                               \
-      if (maxv == 1) PRE(64, VW, 1);       \
-      else if (maxv == 2) PRE(64, VW, 2);  \
-      else if (maxv <= 4) PRE(64, VW, 4);  \
-      else PRE(64, VW, 8);                 \
-  }
-  if (vec4) {
-    PRE_LPB(4)
-  } else {
-    PRE_LPB(1)
-  }
-#undef PRE_LPB
-#undef PRE
-  DLRM_LAUNCH_CHECK(name);
-  return DLRM_OK;
-}
-
-}  // namespace
 
 extern "C" int dlrm_tbe_forward_presort(const float* weights, int64_t D, const int64_t* row_base,
                                         int32_t T, int32_t B, const void* indices,
@@ -1444,9 +1447,10 @@ extern "C" int dlrm_tbe_forward_presort(const float* weights, int64_t D, const i
     DLRM_ARG(mlp_chain_prepare(bottom, mc), "%s: unsupported bottom MLP chain", name);
     mlp_blocks = (int)mlp_chain_blocks(mc);
   }
-  const bool sort = presort_applies((uint64_t)total_rows < 0xFFFFFFFFull ? 4 : 8,
-                                    max_lookups_per_table, num_lookups) &&
-                    num_lookups > 0 && T * (int64_t)B < INT32_MAX;
+  // (32-bit row keys, as in the backward)
+  const bool sort = (uint64_t)total_rows < 0xFFFFFFFFull &&
+                    presort_applies(max_lookups_per_table, num_lookups) && num_lookups > 0 &&
+                    T * (int64_t)B < INT32_MAX;
   // no per-table sort (the backward sorts itself) but a bottom MLP to run: one launch of
   // the lookup and the MLP roles (D <= 512 keeps the gather within its 8 chunks per lane)
   const bool pair = !sort && bottom && out && num_lookups > 0 && T * (int64_t)B < INT32_MAX &&
@@ -1467,16 +1471,35 @@ extern "C" int dlrm_tbe_forward_presort(const float* weights, int64_t D, const i
   DLRM_ARG(out_batch_stride >= (int64_t)T * D, "%s: out_batch_stride < T*D", name);
   DLRM_ARG(workspace || !sort, "%s: null workspace", name);
   hipStream_t st = dlrm::as_stream(stream);
-#define PS(I, O)                                                                           \
-  return launch_fwd_presort<I, O>(weights, D, row_base, T, B, indices, offsets,            \
-                                  per_sample_weights, out, out_batch_stride, num_lookups,  \
-                                  total_rows, workspace, workspace_bytes, error_flag, mc,  \
-                                  mlp_blocks, sort, st)
-  if (index_bits == 32 && offset_bits == 32) PS(int32_t, int32_t);
-  if (index_bits == 32) PS(int32_t, int64_t);
-  if (offset_bits == 32) PS(int64_t, int32_t);
-  PS(int64_t, int64_t);
-#undef PS
+  BwdWs w{};
+  if (sort) {
+    w = carve_bwd_ws(workspace, num_lookups, D);
+    DLRM_REQUIRE(workspace_bytes >= w.total, DLRM_ERR_WORKSPACE,
+                 "%s: workspace %zu < required %zu", name, workspace_bytes, w.total);
+  }
+  const int nsort = sort ? T + 1 : 0;
+  const bool vec4 = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(weights) & 15) == 0) &&
+                    ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && (out_batch_stride % 4 == 0);
+  const LaneGeom g = lane_geom(vec4 ? D / 4 : D);
+  DLRM_REQUIRE(g.maxv <= 8, DLRM_ERR_UNSUPPORTED, "%s: D=%lld too large", name, (long long)D);
+  // out = NULL: the lookup is fused into its consumer (interaction gather)
+  const int64_t gblocks = out ? lane_blocks((int64_t)T * B, g.lpb, kPreThreads / 64) : 0;
+  const dim3 grid((unsigned)(nsort + mlp_blocks + gblocks)), block(kPreThreads);
+  const uint32_t sentinel = (uint32_t)total_rows;
+  for_csr_widths(index_bits, offset_bits, [&](auto i, auto o) {
+    for_row_width(vec4, [&](auto vw) {
+      for_lanes<1, 8>(g, [&](auto lpb, auto mv) {
+        hipLaunchKernelGGL(
+            (tbe_fwd_presort_kernel<decltype(lpb)::value, decltype(vw)::value, decltype(mv)::value,
+                                    width_t<decltype(i)>, width_t<decltype(o)>>),
+            grid, block, 0, st, weights, D, row_base, T, B, i.ptr(indices), o.ptr(offsets),
+            per_sample_weights, out, out_batch_stride, error_flag, num_lookups, sentinel,
+            w.keys_out, w.pos_out, w.bag_of, mc, mlp_blocks, nsort);
+      });
+    });
+  });
+  DLRM_LAUNCH_CHECK(name);
+  return DLRM_OK;
 }
 
 extern "C" int dlrm_mlp_chain_supported(const dlrm_mlp_chain* chain) {

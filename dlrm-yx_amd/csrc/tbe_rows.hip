@@ -18,7 +18,7 @@
 //
 // dlrm_rows_quantize (below the lookup) produces the Q8 / Q4 rows on the device from fp32 or
 // fp16 rows, bitwise torch's packers.
-#include "common.hpp"
+#include "tbe_dispatch.hpp"
 
 namespace {
 
@@ -170,55 +170,21 @@ int64_t min_row_bytes(int fmt, int64_t D) {
   }
 }
 
+// (the entry point has checked D % 4 == 0 and D <= 512: at most 2 float4 chunks per lane)
 template <int FMT, typename IdxT, typename OffT>
 int launch_rows_fwd(const uint8_t* W, int64_t row_bytes, int64_t D, const int64_t* row_base,
-                    int T, int B, const void* idx, const void* off, const float* psw, float* out,
+                    int T, int B, const IdxT* idx, const OffT* off, const float* psw, float* out,
                     int64_t out_bs, int32_t* err, hipStream_t st) {
-  const int64_t nchunks = D / 4;
-  int lpb = 4;
-  while (lpb < nchunks && lpb < 64) lpb <<= 1;
-  const int64_t maxv = dlrm::ceil_div(nchunks, lpb);
-  const int64_t nbags = (int64_t)T * B;
-  const int gpw = 64 / lpb;
-  int64_t blocks = dlrm::ceil_div(dlrm::ceil_div(nbags, gpw), 4);
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  const IdxT* ip = static_cast<const IdxT*>(idx);
-  const OffT* op = static_cast<const OffT*>(off);
-#define RF(LPB, MV)                                                                         \
-  hipLaunchKernelGGL((tbe_rows_fwd_kernel<FMT, LPB, MV, IdxT, OffT>), dim3(blocks), dim3(256), \
-                     0, st, W, row_bytes, D, row_base, T, B, ip, op, psw, out, out_bs, err)
-  switch (lpb) {
-    case 4: RF(4, 1); break;
-    case 8: RF(8, 1); break;
-    case 16: RF(16, 1); break;
-    case 32: RF(32, 1); break;
-    default:
-      if (maxv == 1)
-        RF(64, 1);
-      else
-        RF(64, 2);
-  }
-#undef RF
+  const LaneGeom g = lane_geom(D / 4, 4);
+  const int64_t blocks = lane_blocks((int64_t)T * B, g.lpb, 4);
+  for_lanes<4, 2>(g, [&](auto lpb, auto mv) {
+    hipLaunchKernelGGL(
+        (tbe_rows_fwd_kernel<FMT, decltype(lpb)::value, decltype(mv)::value, IdxT, OffT>),
+        dim3(blocks), dim3(256), 0, st, W, row_bytes, D, row_base, T, B, idx, off, psw, out,
+        out_bs, err);
+  });
   DLRM_LAUNCH_CHECK("dlrm_tbe_forward_rows");
   return DLRM_OK;
-}
-
-template <int FMT>
-int rows_dispatch(const uint8_t* W, int64_t row_bytes, int64_t D, const int64_t* row_base, int T,
-                  int B, const void* idx, int ib, const void* off, int ob, const float* psw,
-                  float* out, int64_t out_bs, int32_t* err, hipStream_t st) {
-  if (ib == 32 && ob == 32)
-    return launch_rows_fwd<FMT, int32_t, int32_t>(W, row_bytes, D, row_base, T, B, idx, off, psw,
-                                                  out, out_bs, err, st);
-  if (ib == 32)
-    return launch_rows_fwd<FMT, int32_t, int64_t>(W, row_bytes, D, row_base, T, B, idx, off, psw,
-                                                  out, out_bs, err, st);
-  if (ob == 32)
-    return launch_rows_fwd<FMT, int64_t, int32_t>(W, row_bytes, D, row_base, T, B, idx, off, psw,
-                                                  out, out_bs, err, st);
-  return launch_rows_fwd<FMT, int64_t, int64_t>(W, row_bytes, D, row_base, T, B, idx, off, psw,
-                                                out, out_bs, err, st);
 }
 
 // ------------------------------------------------------- row-wise quantizer --
@@ -343,29 +309,12 @@ __global__ __launch_bounds__(256) void rows_quantize_kernel(const void* __restri
 
 template <int SRC, int FMT>
 int launch_rows_quantize(const void* src, int64_t rows, int D, uint8_t* dst, hipStream_t st) {
-  const int nchunks = D / 4;
-  int lpb = 1;
-  while (lpb < nchunks && lpb < 64) lpb <<= 1;
-  const int gpw = 64 / lpb;
-  int64_t blocks = dlrm::ceil_div(dlrm::ceil_div(rows, (int64_t)gpw), 4);
-  if (blocks > 8192) blocks = 8192;
-#define RQ(LPB, MV)                                                                           \
-  hipLaunchKernelGGL((rows_quantize_kernel<SRC, FMT, LPB, MV>), dim3(blocks), dim3(256), 0, st, \
-                     src, rows, D, dst)
-  switch (lpb) {
-    case 1: RQ(1, 1); break;
-    case 2: RQ(2, 1); break;
-    case 4: RQ(4, 1); break;
-    case 8: RQ(8, 1); break;
-    case 16: RQ(16, 1); break;
-    case 32: RQ(32, 1); break;
-    default:
-      if (nchunks <= 64)
-        RQ(64, 1);
-      else
-        RQ(64, 2);
-  }
-#undef RQ
+  const LaneGeom g = lane_geom(D / 4);  // (D <= 512: at most 2 chunks per lane)
+  const int64_t blocks = lane_blocks(rows, g.lpb, 4);
+  for_lanes<1, 2>(g, [&](auto lpb, auto mv) {
+    hipLaunchKernelGGL((rows_quantize_kernel<SRC, FMT, decltype(lpb)::value, decltype(mv)::value>),
+                       dim3(blocks), dim3(256), 0, st, src, rows, D, dst);
+  });
   DLRM_LAUNCH_CHECK("dlrm_rows_quantize");
   return DLRM_OK;
 }
@@ -428,18 +377,17 @@ extern "C" int dlrm_tbe_forward_rows(const void* weights, int32_t format, int64_
   if ((int64_t)T * B == 0) return DLRM_OK;
   hipStream_t st = dlrm::as_stream(stream);
   const uint8_t* W = static_cast<const uint8_t*>(weights);
-  switch (format) {
-    case DLRM_ROWS_F16:
-      return rows_dispatch<DLRM_ROWS_F16>(W, row_bytes, D, row_base, T, B, indices, index_bits,
-                                          offsets, offset_bits, per_sample_weights, out,
-                                          out_batch_stride, error_flag, st);
-    case DLRM_ROWS_Q8:
-      return rows_dispatch<DLRM_ROWS_Q8>(W, row_bytes, D, row_base, T, B, indices, index_bits,
-                                         offsets, offset_bits, per_sample_weights, out,
-                                         out_batch_stride, error_flag, st);
-    default:
-      return rows_dispatch<DLRM_ROWS_Q4>(W, row_bytes, D, row_base, T, B, indices, index_bits,
-                                         offsets, offset_bits, per_sample_weights, out,
-                                         out_batch_stride, error_flag, st);
-  }
+  return for_csr_widths(index_bits, offset_bits, [&](auto i, auto o) {
+    const auto lookup = [&](auto fmt) {
+      return launch_rows_fwd<decltype(fmt)::value>(W, row_bytes, D, row_base, T, B,
+                                                   i.ptr(indices), o.ptr(offsets),
+                                                   per_sample_weights, out, out_batch_stride,
+                                                   error_flag, st);
+    };
+    switch (format) {
+      case DLRM_ROWS_F16: return lookup(int_tag<DLRM_ROWS_F16>{});
+      case DLRM_ROWS_Q8: return lookup(int_tag<DLRM_ROWS_Q8>{});
+      default: return lookup(int_tag<DLRM_ROWS_Q4>{});
+    }
+  });
 }

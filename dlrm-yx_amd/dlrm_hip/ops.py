@@ -370,6 +370,35 @@ def tbe_backward_workspace_size(num_lookups: int, total_rows: int, D: int) -> in
 PRESORTED_ANY = 2  # DLRM_PRESORTED_ANY
 
 
+def _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights, workspace,
+                  max_lookups_per_table, error_flag, grad=None):
+    """What the backward entry points share, as (head, tail) of their argument lists: head is
+    D .. per_sample_weights, then ``grad`` = (grad_out, its batch stride or None for T * D)
+    where there is a gradient; tail is the table bound, the workspace (by default this
+    module's own, grown to the call's size), its size and the error flag."""
+    D, N, total_rows = weights.shape[1], indices.numel(), weights.shape[0]
+    head = (D, _p(row_base), T, B, _p(indices), _bits(indices), _p(offsets), _bits(offsets), N,
+            total_rows, _p(per_sample_weights))
+    if grad is not None:
+        head += (_p(grad[0]), T * D if grad[1] is None else grad[1])
+    if workspace is None:
+        workspace = _ws("tbe_bwd", tbe_backward_workspace_size(N, total_rows, D), weights.device)
+    return head, (int(max_lookups_per_table), _p(workspace), workspace.numel(), _p(error_flag))
+
+
+# tbe_backward's entry points: the name, whether momentum= is passed, how the rate is passed
+# ("split": the float to the entry or the device pointer to its _dev twin; "both": the float,
+# 0 beside a device rate, and the pointer; None: no rate), and whether eps is passed
+_TBE_BWD = {
+    "sgd": ("dlrm_tbe_backward_sgd", False, "split", False),
+    "sgd_f16": ("dlrm_tbe_backward_sgd_f16", False, "split", False),
+    "rowwise_adagrad": ("dlrm_tbe_backward_rowwise_adagrad", True, "split", True),
+    "adagrad": ("dlrm_tbe_backward_adagrad", True, "both", True),
+    "dense": ("dlrm_tbe_backward_dense", False, None, False),
+}
+_TBE_BWD_SR = ("dlrm_tbe_backward_sgd_f16_sr", False, "both", False)  # then the sr state
+
+
 def tbe_backward_sort(weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
                       indices: torch.Tensor, offsets: torch.Tensor, workspace: torch.Tensor,
                       max_lookups_per_table: int = 0,
@@ -380,10 +409,9 @@ def tbe_backward_sort(weights: torch.Tensor, row_base: torch.Tensor, T: int, B: 
     tbe_backward(..., workspace, presorted=PRESORTED_ANY) of the same batch (same bound and
     per_sample_weights nullness)."""
     _check_cuda(weights, row_base, indices, offsets, workspace, per_sample_weights)
-    _lib.call("dlrm_tbe_backward_sort", weights.shape[1], _p(row_base), T, B, _p(indices),
-              _bits(indices), _p(offsets), _bits(offsets), indices.numel(), weights.shape[0],
-              _p(per_sample_weights), int(max_lookups_per_table), _p(workspace),
-              workspace.numel(), _p(error_flag), _stream(weights.device))
+    head, tail = _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights,
+                               workspace, max_lookups_per_table, error_flag)
+    _lib.call("dlrm_tbe_backward_sort", *head, *tail, _stream(weights.device))
 
 
 def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
@@ -416,48 +444,20 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     if sr_state is not None and not (mode in ("sgd", "sgd_f16")
                                      and weights.dtype == torch.float16):
         raise ValueError("tbe_backward: sr_state goes with 'sgd' / 'sgd_f16' on fp16 weights")
-    D = weights.shape[1]
-    N = indices.numel()
-    total_rows = weights.shape[0]
-    if grad_batch_stride is None:
-        grad_batch_stride = T * D
-    need = tbe_backward_workspace_size(N, total_rows, D)
-    if workspace is None:
-        workspace = _ws("tbe_bwd", need, weights.device)
-    args_common = (D, _p(row_base), T, B, _p(indices), _bits(indices), _p(offsets),
-                   _bits(offsets), N, total_rows, _p(per_sample_weights), _p(grad_out),
-                   grad_batch_stride)
-    st = _stream(weights.device)
-    mx = int(max_lookups_per_table)
+    head, tail = _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights,
+                               workspace, max_lookups_per_table, error_flag,
+                               (grad_out, grad_batch_stride))
     if mode == "sgd_f16" and weights.dtype != torch.float16:
         raise ValueError("tbe_backward: mode 'sgd_f16' takes fp16 weights")
     if sr_state is not None:
-        _lib.call("dlrm_tbe_backward_sgd_f16_sr", _p(weights), *args_common,
-                  0.0 if lr_dev is not None else lr, lr_dev,
-                  _sr_ptr(sr_state, "tbe_backward"), mx, _p(workspace), workspace.numel(),
-                  _p(error_flag), int(presorted), st)
+        entry = _TBE_BWD_SR
     elif mode in ("sgd", "sgd_f16") and weights.dtype == torch.float16:
-        if lr_dev is not None:
-            _lib.call("dlrm_tbe_backward_sgd_f16_dev", _p(weights), *args_common, lr_dev, mx,
-                      _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
-        else:
-            _lib.call("dlrm_tbe_backward_sgd_f16", _p(weights), *args_common, lr, mx,
-                      _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
-    elif mode == "sgd" and lr_dev is not None:
-        _lib.call("dlrm_tbe_backward_sgd_dev", _p(weights), *args_common, lr_dev, mx,
-                  _p(workspace), workspace.numel(), _p(error_flag), int(presorted), st)
-    elif mode == "sgd":
-        _lib.call("dlrm_tbe_backward_sgd", _p(weights), *args_common, lr, mx, _p(workspace),
-                  workspace.numel(), _p(error_flag), int(presorted), st)
-    elif mode == "rowwise_adagrad" and lr_dev is not None:
-        _lib.call("dlrm_tbe_backward_rowwise_adagrad_dev", _p(weights), _p(momentum),
-                  *args_common, lr_dev, eps, mx, _p(workspace), workspace.numel(),
-                  _p(error_flag), int(presorted), st)
-    elif mode == "rowwise_adagrad":
-        _lib.call("dlrm_tbe_backward_rowwise_adagrad", _p(weights), _p(momentum), *args_common,
-                  lr, eps, mx, _p(workspace), workspace.numel(), _p(error_flag), int(presorted),
-                  st)
-    elif mode == "adagrad":
+        entry = _TBE_BWD["sgd_f16"]
+    elif mode in _TBE_BWD:
+        entry = _TBE_BWD[mode]
+    else:
+        raise ValueError(mode)
+    if mode == "adagrad":
         if weights.dtype != torch.float32:
             raise ValueError("tbe_backward: mode 'adagrad' takes fp32 weights")
         if (momentum is None or momentum.dtype != torch.float32
@@ -466,14 +466,17 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
             raise ValueError("tbe_backward: mode 'adagrad' takes its state as momentum=, a "
                              f"contiguous fp32 tensor of the weights' shape "
                              f"{tuple(weights.shape)}")
-        _lib.call("dlrm_tbe_backward_adagrad", _p(weights), _p(momentum), *args_common,
-                  0.0 if lr_dev is not None else lr, lr_dev, eps, mx, _p(workspace),
-                  workspace.numel(), _p(error_flag), int(presorted), st)
-    elif mode == "dense":
-        _lib.call("dlrm_tbe_backward_dense", _p(weights), *args_common, mx, _p(workspace),
-                  workspace.numel(), _p(error_flag), int(presorted), st)
-    else:
-        raise ValueError(mode)
+    name, with_state, rate_as, with_eps = entry
+    rate = ()
+    if rate_as == "both":
+        rate = (0.0 if lr_dev is not None else lr, lr_dev)
+    elif rate_as == "split":
+        rate = (lr,) if lr_dev is None else (lr_dev,)
+        name += "" if lr_dev is None else "_dev"
+    if sr_state is not None:
+        rate += (_sr_ptr(sr_state, "tbe_backward"),)
+    _lib.call(name, _p(weights), *((_p(momentum),) if with_state else ()), *head, *rate,
+              *((eps,) if with_eps else ()), *tail, int(presorted), _stream(weights.device))
 
 
 def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
@@ -494,23 +497,15 @@ def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor,
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     if weights.dtype != torch.float32 or mode not in ("sgd", "rowwise_adagrad"):
         raise ValueError("tbe_backward_defer: fp32 'sgd' or 'rowwise_adagrad' only")
-    D = weights.shape[1]
-    N = indices.numel()
-    total_rows = weights.shape[0]
-    if grad_batch_stride is None:
-        grad_batch_stride = T * D
-    need = tbe_backward_workspace_size(N, total_rows, D)
-    if workspace is None:
-        workspace = _ws("tbe_bwd", need, weights.device)
+    head, tail = _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights,
+                               workspace, max_lookups_per_table, error_flag,
+                               (grad_out, grad_batch_stride))
     role = _lib.LaunchRole()
     lr_dev = _lr_dev(lr, "tbe_backward_defer: lr")
     _lib.call("dlrm_tbe_backward_defer" if lr_dev is None else "dlrm_tbe_backward_defer_dev",
-              0 if mode == "sgd" else 1, _p(weights), _p(momentum),
-              D, _p(row_base), T, B, _p(indices), _bits(indices), _p(offsets), _bits(offsets), N,
-              total_rows, _p(per_sample_weights), _p(grad_out), grad_batch_stride,
-              lr if lr_dev is None else lr_dev, eps,
-              int(max_lookups_per_table), _p(workspace), workspace.numel(), _p(error_flag),
-              int(presorted), ctypes.byref(role), _stream(weights.device))
+              0 if mode == "sgd" else 1, _p(weights), _p(momentum), *head,
+              lr if lr_dev is None else lr_dev, eps, *tail, int(presorted), ctypes.byref(role),
+              _stream(weights.device))
     return role if role_blocks(role) > 0 else None
 
 
