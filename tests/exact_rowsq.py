@@ -72,7 +72,10 @@ def fma32(a, b, c):
     """fp32 fma(a, b, c) with ONE rounding, for fp32 a, c and small integer b (a * b is then
     exact in fp64).  The fp64 sum is rounded to odd (TwoSum gives the exact error; an inexact
     sum with an even last bit moves one ulp towards the error), and a round-to-odd 53-bit value
-    rounds to nearest-even fp32 as the exact value does: no double rounding."""
+    rounds to nearest-even fp32 as the exact value does: no double rounding.  The same holds
+    for any b whose product with a is exact in fp64: an fp16 value widened to fp32 (a 24-bit
+    times an 11-bit significand: 35 bits, the F16 lookup of exact_rows_lookup.py) or another
+    fp32 value (48 bits)."""
     p = np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64)
     c = np.broadcast_to(np.asarray(c, dtype=np.float64), p.shape)
     s = p + c

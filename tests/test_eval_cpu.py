@@ -47,6 +47,45 @@ def test_eval_ref_vs_sklearn(case):
         assert fin[k] == got[k], k
 
 
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_vectorised_a2_is_the_python_integer_loop(case):
+    """metrics_from_keys sums A2 in int64 (so millions of groups are affordable): the same
+    integers as the group-by-group python loop it replaced, and an exactly rounded ap beside
+    numpy's."""
+    name, prob, lab = case
+    keys = eval_ref.pack_keys(prob, lab)
+    fast, slow = eval_ref.metrics_from_keys(keys), eval_ref.metrics_from_keys(keys, slow=True)
+    for k in ("a2", "n_pos", "n_neg", "groups"):
+        assert type(fast[k]) is int and fast[k] == slow[k], k
+    assert fast["ap"] == slow["ap"] and fast["ap_fsum"] == slow["ap_fsum"]
+    assert abs(fast["ap"] - fast["ap_fsum"]) <= 1e-13
+    assert fast["a2"] <= 2 * fast["n_pos"] * fast["n_neg"]
+
+
+def test_big_inputs_reach_the_multi_tile_plan():
+    """The plans test_gpu_eval.py::test_metrics_many_tiles_per_workgroup relies on, from the
+    kernel's own constants."""
+    with open(os.path.join(ROOT, "dlrm-yx_amd", "csrc", "metrics.hip")) as f:
+        src = f.read()
+    assert int(re.search(r"kMaxSortWgs\s*=\s*(\d+)", src).group(1)) == eval_ref.MAX_SORT_WGS
+    tile = ops.EVAL_SORT_TILE
+    assert eval_ref.sort_plan(70001, tile) == (18, 1, 18)  # the largest shared input
+    assert eval_ref.sort_plan(eval_ref.MAX_SORT_WGS * tile, tile) == (1024, 1, 1024)
+    want = {"big_distinct": (1025, 2, 513), "big_ties": (1025, 2, 513),
+            "big_three": (2052, 3, 684)}
+    for name in eval_ref.BIG_NAMES:
+        prob, lab = eval_ref.big_input(name, tile)
+        assert prob.dtype == lab.dtype == np.float32 and prob.size == lab.size
+        assert eval_ref.sort_plan(prob.size, tile) == want[name], name
+        assert 0 < lab.sum() < lab.size and prob.min() >= 0 and prob.max() <= 1
+    prob, _ = eval_ref.big_input("big_distinct", tile)
+    assert np.unique(prob).size == prob.size
+    prob, _ = eval_ref.big_input("big_ties", tile)
+    assert np.unique(prob).size == 1000
+    prob, _ = eval_ref.big_input("big_three", tile)
+    assert prob.size // 7 <= (prob == np.float32(0.5)).sum() <= prob.size // 7 + 2
+
+
 def test_equal_scores_give_half():
     _, prob, lab = [c for c in CASES if c[0] == "equal"][0]
     got = eval_ref.full(prob, lab)

@@ -104,6 +104,53 @@ def test_update_and_metrics_vs_ref(name):
     assert np.array_equal(_u32(st.keys), ref["sorted"])  # compute sorts the log in place
 
 
+@pytest.mark.parametrize("name", eval_ref.BIG_NAMES)
+def test_metrics_many_tiles_per_workgroup(name):
+    """More than kMaxSortWgs tiles: every sort workgroup walks a run of tiles, so the tile
+    loops of sort_hist_kernel / sort_scatter_kernel, the carry of each digit's destination
+    from a workgroup's tile to its next, hist_row_scan_kernel with hundreds of live entries
+    and scan_u32_kernel / group_final_kernel with more than 256 tiles (a chunk above 1, more
+    than one partial per thread) all run.  Integers and sorted keys are exact."""
+    metrics, ops = _mods()
+    tile = ops.EVAL_SORT_TILE
+    prob, lab = eval_ref.big_input(name, tile)
+    n = prob.size
+    ntiles, per_wg, wgs = eval_ref.sort_plan(n, tile)
+    assert (ntiles, per_wg, wgs) == dict(big_distinct=(1025, 2, 513), big_ties=(1025, 2, 513),
+                                         big_three=(2052, 3, 684))[name]
+    assert ntiles == -(-n // tile) > 1024 and per_wg > 1 and (ntiles - 1) // per_wg == wgs - 1
+    ref = _ref(name, prob, lab)
+    if name == "big_distinct":
+        assert ref["groups"] == n
+    st = metrics.EvalState(n, dev)
+    st.update(torch.tensor(prob, device=dev), torch.tensor(lab, device=dev))  # one call
+    assert st.count == n
+    _same_ints(_counts(st), ref, ("tp", "fp", "tn", "fn"))
+    assert np.array_equal(_u32(st.keys), eval_ref.pack_keys(prob, lab))  # log order
+    # |ap - ap_fsum| <= (h + 8) 2^-53 ap_fsum.  h = 32 + ceil(ntiles / 256) is the deepest
+    # addition chain of the device's fixed-order sum: a thread adds its 16 terms serially,
+    # an 8-level tree joins the tile's 256 threads, then a thread adds ceil(ntiles / 256) tile
+    # partials serially and another 8-level tree follows; every term is non-negative, so each
+    # addition costs at most 2^-53 of the total.  Each term carries three roundings (two
+    # divisions and a product) on the device and three in the reference: 6; fsum rounds
+    # once: 1/2; the rest is slack for the second-order terms.
+    h = 32 + -(-ntiles // 256)
+    bound = (h + 8) * 2.0 ** -53 * ref["ap_fsum"]
+    outs = []
+    for _ in range(2):
+        keys = st.keys.clone()
+        out = ops.eval_metrics(keys)
+        assert np.array_equal(_u32(keys), ref["sorted"])
+        _same_ints(_ints(out), ref, ("a2", "n_pos", "n_neg", "groups"))
+        ap = _ap(out)
+        print(name, "ap", repr(ap), "ref", repr(ref["ap"]), "diff", abs(ap - ref["ap"]),
+              "fsum", repr(ref["ap_fsum"]), "diff", abs(ap - ref["ap_fsum"]), "bound", bound)
+        assert abs(ap - ref["ap"]) <= 1e-12
+        assert abs(ap - ref["ap_fsum"]) <= bound
+        outs.append(out.cpu())
+    assert torch.equal(outs[0], outs[1])  # two runs: bitwise-equal ap and integers
+
+
 def test_appending_in_pieces():
     metrics, ops = _mods()
     _, prob, lab = [c for c in _cases() if c[0] == "distinct"][0]
