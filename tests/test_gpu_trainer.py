@@ -94,9 +94,43 @@ def _rand_batch(rng, rows, B, L, m_den, loss, dist="uniform"):
     return X, lS_o, lS_i, T
 
 
+def _oracle_tensors(ref):
+    """name -> parameter of an oracle (tables, then W / b per layer, bottom MLP first)."""
+    out = {f"table{k}": e.weight for k, e in enumerate(ref.emb_l)}
+    lin = [m for seq in (ref.bot_l, ref.top_l) for m in seq if isinstance(m, torch.nn.Linear)]
+    for i, m in enumerate(lin):
+        out[f"W{i}"], out[f"b{i}"] = m.weight, m.bias
+    return {k: v.detach().numpy().copy() for k, v in out.items()}
+
+
+def _engine_tensors(tr):
+    out = {f"table{k}": tr.table(k).cpu().numpy() for k in range(tr.T)}
+    for i, (W, b) in enumerate(tr.dense_state()):
+        out[f"W{i}"], out[f"b{i}"] = W.cpu().numpy(), b.cpu().numpy()
+    return out
+
+
+def _update_check(name, before, tr, ref, ref64, lS_i):
+    """The first step's updates, per tensor, through update_close.check (engine against the
+    fp64 twin, in units of the fp32 oracle's own distance from it); rows of a table that no
+    index names keep their bits.  Returns {tensor: (d, e, max |update|)}."""
+    import update_close as U
+    got, o32, o64 = _engine_tensors(tr), _oracle_tensors(ref), _oracle_tensors(ref64)
+    out = {}
+    for k in before:
+        touched = None
+        if k.startswith("table"):
+            touched = np.zeros(before[k].shape[0], dtype=bool)
+            touched[np.asarray(lS_i[int(k[5:])])] = True
+        out[k] = U.check(name, k, before[k], got[k], o32[k], o64[k], touched)
+    return out
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_step_vs_oracle(name):
-    """Two steps vs the oracle."""
+    """Two steps vs the oracle; the first step's updates also through update_close (both
+    sides start it from identical weights)."""
+    import train16_ref as T16
     DLRMTrainer, TrainerConfig = _trainer()
     c = CASES[name]
     D, rows = c["D"], c["rows"]
@@ -106,6 +140,7 @@ def test_step_vs_oracle(name):
     cfg = TrainerConfig(m_spa=D, ln_emb=rows, ln_bot=c["bot"], ln_top=ln_top,
                         loss_function=c["loss"], learning_rate=c["lr"])
     tr = DLRMTrainer.from_oracle(cfg, ref, device=dev)
+    ref64, before = T16.clone64(ref), _oracle_tensors(ref)
     rng = np.random.RandomState(3)
     for s in range(2):
         X, lS_o, lS_i, T = _rand_batch(rng, rows, c["B"], c["L"], c["bot"][0], c["loss"])
@@ -116,6 +151,9 @@ def test_step_vs_oracle(name):
         assert ok, (s, msg)
         ok, msg = fp32_close(E.cpu().numpy(), [Er.item()])
         assert ok, (s, msg)
+        if s == 0:
+            T16.train_step(ref64, X, lS_o, lS_i, T, c["lr"])
+            _update_check(name, before, tr, ref, ref64, lS_i)
     _compare_state(tr, ref)
 
 
