@@ -36,6 +36,25 @@ __device__ __forceinline__ float dlrm_resolve_lr(const float* lr_dev, float lr) 
   typedef const float __attribute__((address_space(4))) * const_f32;
   return lr_dev ? *(const_f32)lr_dev : lr;
 }
+
+// The arithmetic of every scaled epilogue and fused SGD update: alpha * acc is rounded alone
+// (dlrm_scale), then one rounded add or subtract - fl(old - fl(alpha * acc)), two roundings.
+// Written as plain operators under contract(off), not as __fmul_rn / __fsub_rn / __fadd_rn:
+// the HIP headers define those as `x * y`, `x - y`, `x + y` compiled under the translation
+// unit's -ffp-contract=fast, and once inlined the pair does fuse into one v_fma_f32.  A
+// product or sum without the contract flag fuses with nothing, whatever it is inlined into.
+__device__ __forceinline__ float dlrm_scale(float alpha, float acc) {
+#pragma clang fp contract(off)
+  return alpha * acc;
+}
+__device__ __forceinline__ float dlrm_sgd_step(float old, float scaled) {
+#pragma clang fp contract(off)
+  return old - scaled;
+}
+__device__ __forceinline__ float dlrm_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
 #endif
 
 #define DLRM_REQUIRE(cond, code, ...)   \

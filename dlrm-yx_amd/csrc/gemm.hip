@@ -297,48 +297,61 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
-// C = epilogue(v) where v = alpha * acc (already scaled); returns the value written.
-__device__ __forceinline__ float apply_epilogue(const GemmParams& p, int64_t row, int64_t col,
-                                                float v) {
-  float* cp = p.C + row * p.ldc + col;
-  switch (p.epi) {
-    case DLRM_EPI_BIAS:
-      v += p.bias[col];
-      break;
-    case DLRM_EPI_BIAS_RELU:
-      v = fmaxf(v + p.bias[col], 0.f);
-      break;
-    case DLRM_EPI_RELU:
-      v = fmaxf(v, 0.f);
-      break;
-    case DLRM_EPI_DRELU:
-      v = p.aux[row * p.ldaux + col] > 0.f ? v : 0.f;
-      break;
-    case DLRM_EPI_SGD:
-      v = *cp - v;
-      break;
-    case DLRM_EPI_ACCUM:
-      v = *cp + v;
-      break;
-    default:
-      break;
-  }
-  *cp = v;
-  return v;
-}
-
-// The same epilogue for a compile-time kind, on values already loaded: old = the C element
-// (SGD / ACCUM), aux = the mask operand (DRELU), bias = bias[col] (BIAS / BIAS_RELU).  The
-// arithmetic is apply_epilogue's, so results are bitwise the same.
+// The epilogue arithmetic, spelled once: v = dlrm_scale(alpha, acc), rounded alone, then at
+// most one rounded add or subtract (common.hpp) - SGD is fl(old - fl(alpha * acc)).  Every
+// output path of this file ends here, so all of them give the same bits.  old = the C
+// element (SGD / ACCUM), aux = the mask operand (DRELU), bias = bias[col] (BIAS / BIAS_RELU).
 template <int EPI>
 __device__ __forceinline__ float epi_value(float v, float old, float aux, float bias) {
-  if constexpr (EPI == DLRM_EPI_BIAS) return v + bias;
-  else if constexpr (EPI == DLRM_EPI_BIAS_RELU) return fmaxf(v + bias, 0.f);
+  if constexpr (EPI == DLRM_EPI_BIAS) return dlrm_add_rn(v, bias);
+  else if constexpr (EPI == DLRM_EPI_BIAS_RELU) return fmaxf(dlrm_add_rn(v, bias), 0.f);
   else if constexpr (EPI == DLRM_EPI_RELU) return fmaxf(v, 0.f);
   else if constexpr (EPI == DLRM_EPI_DRELU) return aux > 0.f ? v : 0.f;
-  else if constexpr (EPI == DLRM_EPI_SGD) return old - v;
-  else if constexpr (EPI == DLRM_EPI_ACCUM) return old + v;
+  else if constexpr (EPI == DLRM_EPI_SGD) return dlrm_sgd_step(old, v);
+  else if constexpr (EPI == DLRM_EPI_ACCUM) return dlrm_add_rn(old, v);
   else return v;
+}
+
+// f(integral_constant<int, kind>) for the runtime kind.
+template <typename F>
+__device__ __forceinline__ void epi_dispatch(int epi, F&& f) {
+  switch (epi) {
+    case DLRM_EPI_BIAS: return f(std::integral_constant<int, DLRM_EPI_BIAS>{});
+    case DLRM_EPI_BIAS_RELU: return f(std::integral_constant<int, DLRM_EPI_BIAS_RELU>{});
+    case DLRM_EPI_RELU: return f(std::integral_constant<int, DLRM_EPI_RELU>{});
+    case DLRM_EPI_DRELU: return f(std::integral_constant<int, DLRM_EPI_DRELU>{});
+    case DLRM_EPI_SGD: return f(std::integral_constant<int, DLRM_EPI_SGD>{});
+    case DLRM_EPI_ACCUM: return f(std::integral_constant<int, DLRM_EPI_ACCUM>{});
+    default: return f(std::integral_constant<int, DLRM_EPI_STORE>{});
+  }
+}
+
+// The slow paths' store (64-bit addresses, guarded by the caller): C[row][col + q] =
+// epi(alpha * acc[q]) for NE consecutive columns, the operand loads in flight together.
+template <int NE>
+__device__ __forceinline__ void store_epilogue(const GemmParams& p, int64_t row, int64_t col,
+                                               float alpha, const float (&acc)[NE]) {
+  float* cp = p.C + row * p.ldc + col;
+  float v[NE];
+#pragma unroll
+  for (int q = 0; q < NE; ++q) v[q] = dlrm_scale(alpha, acc[q]);
+  epi_dispatch(p.epi, [&](auto kind) {
+    constexpr int EPI = decltype(kind)::value;
+    float old[NE], aux[NE], bias[NE];
+#pragma unroll
+    for (int q = 0; q < NE; ++q) {
+      old[q] = (EPI == DLRM_EPI_SGD || EPI == DLRM_EPI_ACCUM) ? cp[q] : 0.f;
+      aux[q] = EPI == DLRM_EPI_DRELU ? p.aux[row * p.ldaux + col + q] : 0.f;
+      bias[q] = (EPI == DLRM_EPI_BIAS || EPI == DLRM_EPI_BIAS_RELU) ? p.bias[col + q] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < NE; ++q) cp[q] = epi_value<EPI>(v[q], old[q], aux[q], bias[q]);
+  });
+}
+__device__ __forceinline__ void store_epilogue(const GemmParams& p, int64_t row, int64_t col,
+                                               float alpha, float acc) {
+  const float one[1] = {acc};
+  store_epilogue<1>(p, row, col, alpha, one);
 }
 
 __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int off) {
@@ -397,15 +410,7 @@ template <int NE>
 __device__ __forceinline__ void store_elems_any(const GemmParams& p, const int (&row)[NE],
                                                 const int (&col)[NE], const bool (&ok)[NE],
                                                 const float (&v)[NE]) {
-  switch (p.epi) {
-    case DLRM_EPI_BIAS: return store_elems<DLRM_EPI_BIAS>(p, row, col, ok, v);
-    case DLRM_EPI_BIAS_RELU: return store_elems<DLRM_EPI_BIAS_RELU>(p, row, col, ok, v);
-    case DLRM_EPI_RELU: return store_elems<DLRM_EPI_RELU>(p, row, col, ok, v);
-    case DLRM_EPI_DRELU: return store_elems<DLRM_EPI_DRELU>(p, row, col, ok, v);
-    case DLRM_EPI_SGD: return store_elems<DLRM_EPI_SGD>(p, row, col, ok, v);
-    case DLRM_EPI_ACCUM: return store_elems<DLRM_EPI_ACCUM>(p, row, col, ok, v);
-    default: return store_elems<DLRM_EPI_STORE>(p, row, col, ok, v);
-  }
+  epi_dispatch(p.epi, [&](auto kind) { store_elems<decltype(kind)::value>(p, row, col, ok, v); });
 }
 
 
@@ -523,47 +528,38 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, float alpha,
     for (int j = 0; j < FN; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[(i * FN + j) * 4 + r] = acc[i][j][r];
-  if (p.mode == DLRM_GEMM_PARTIAL && p.M * p.N * 4 < 0x7ff00000LL) {
-    // raw partial sums for a REDUCE job of a later launch (the kernel boundary publishes),
-    // as buffer stores from one descriptor per slab: no per-element branch or 64-bit address
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.part + (int64_t)split * p.M * p.N), (short)0, (int)(p.M * p.N * 4), 0x00020000);
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int col = (int)(n0 + wn0 + j * 16 + l16);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = (int)(m0 + wm0 + i * 16 + 4 * kq + r);
-          buf_st(v[(i * FN + j) * 4 + r], rp,
-                 row < p.M && col < p.N ? (int)(((int64_t)row * p.N + col) * 4) : kOob);
-        }
-      }
-    if (rs_owner) {
-      float* rslab = p.part + (int64_t)p.splits * p.M * p.N + (int64_t)split * p.M;
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const int64_t row = m0 + wm0 + i * 16 + l16;
-        if (row < p.M) rslab[row] = rs[i];
-      }
-    }
-    return;
-  }
   if (p.mode == DLRM_GEMM_PARTIAL) {
     // raw partial sums for a REDUCE job of a later launch (the kernel boundary publishes)
     float* slab = p.part + (int64_t)split * p.M * p.N;
+    if (p.M * p.N * 4 < 0x7ff00000LL) {
+      // buffer stores from one descriptor per slab: no per-element branch or 64-bit address
+      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)slab, (short)0, (int)(p.M * p.N * 4), 0x00020000);
 #pragma unroll
-    for (int i = 0; i < FM; ++i)
+      for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int64_t col = n0 + wn0 + j * 16 + l16;
+        for (int j = 0; j < FN; ++j) {
+          const int col = (int)(n0 + wn0 + j * 16 + l16);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t row = m0 + wm0 + i * 16 + 4 * kq + r;
-          if (row < p.M && col < p.N) slab[row * p.N + col] = v[(i * FN + j) * 4 + r];
+          for (int r = 0; r < 4; ++r) {
+            const int row = (int)(m0 + wm0 + i * 16 + 4 * kq + r);
+            buf_st(v[(i * FN + j) * 4 + r], rp,
+                   row < p.M && col < p.N ? (int)(((int64_t)row * p.N + col) * 4) : kOob);
+          }
         }
-      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const int64_t col = n0 + wn0 + j * 16 + l16;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int64_t row = m0 + wm0 + i * 16 + 4 * kq + r;
+            if (row < p.M && col < p.N) slab[row * p.N + col] = v[(i * FN + j) * 4 + r];
+          }
+        }
+    }
     if (rs_owner) {
       float* rslab = p.part + (int64_t)p.splits * p.M * p.N + (int64_t)split * p.M;
 #pragma unroll
@@ -590,7 +586,7 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, float alpha,
           row[q] = (int)(m0 + wm0 + i * 16 + 4 * kq + r);
           col[q] = (int)(n0 + wn0 + j * 16 + l16);
           ok[q] = col[q] < p.N;
-          w[q] = __fmul_rn(alpha, v[q]);  // rounded alone, as apply_epilogue sees it
+          w[q] = dlrm_scale(alpha, v[q]);
         }
     store_elems_any<NV>(p, row, col, ok, w);
     if constexpr (RS) {
@@ -602,7 +598,7 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, float alpha,
         rrow[i] = (int)(m0 + wm0 + i * 16 + l16);
         rcol[i] = (int)p.ones_col;
         rok[i] = rs_owner;
-        rw[i] = __fmul_rn(alpha, rs[i]);
+        rw[i] = dlrm_scale(alpha, rs[i]);
       }
       store_elems_any<FM>(p, rrow, rcol, rok, rw);
     }
@@ -616,14 +612,14 @@ __device__ __forceinline__ void finish_tile(const GemmParams& p, float alpha,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = m0 + wm0 + i * 16 + 4 * kq + r;
-        if (row < p.M && col < p.N) apply_epilogue(p, row, col, alpha * v[(i * FN + j) * 4 + r]);
+        if (row < p.M && col < p.N) store_epilogue(p, row, col, alpha, v[(i * FN + j) * 4 + r]);
       }
     }
   if (rs_owner) {
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
       const int64_t row = m0 + wm0 + i * 16 + l16;
-      if (row < p.M) apply_epilogue(p, row, p.ones_col, alpha * rs[i]);
+      if (row < p.M) store_epilogue(p, row, p.ones_col, alpha, rs[i]);
     }
   }
 }
@@ -888,31 +884,14 @@ __device__ __forceinline__ void reduce_body(const GemmParams& p, int lb) {
         }
     }
     const int64_t e = 4 * i, row = e / p.N, col = e - row * p.N;
-    if (p.epi == DLRM_EPI_SGD || p.epi == DLRM_EPI_ACCUM) {
-      // the four old values loaded together (the generic path waits for each in turn)
-      float* cp = p.C + row * p.ldc + col;
-      const float o0 = cp[0], o1 = cp[1], o2 = cp[2], o3 = cp[3];
-      const bool sgd = p.epi == DLRM_EPI_SGD;
-      // alpha * acc rounded on its own (no contraction into the add): apply_epilogue's
-      // arithmetic, bitwise
-      const float v0 = __fmul_rn(alpha, acc.x), v1 = __fmul_rn(alpha, acc.y);
-      const float v2 = __fmul_rn(alpha, acc.z), v3 = __fmul_rn(alpha, acc.w);
-      cp[0] = sgd ? o0 - v0 : o0 + v0;
-      cp[1] = sgd ? o1 - v1 : o1 + v1;
-      cp[2] = sgd ? o2 - v2 : o2 + v2;
-      cp[3] = sgd ? o3 - v3 : o3 + v3;
-      return;
-    }
-    apply_epilogue(p, row, col, alpha * acc.x);
-    apply_epilogue(p, row, col + 1, alpha * acc.y);
-    apply_epilogue(p, row, col + 2, alpha * acc.z);
-    apply_epilogue(p, row, col + 3, alpha * acc.w);
+    const float a4[4] = {acc.x, acc.y, acc.z, acc.w};
+    store_epilogue<4>(p, row, col, alpha, a4);  // SGD / ACCUM: four old values in flight
   } else if (p.ones_col >= 0 && i - n4 < p.M) {
     const int64_t row = i - n4;
     const float* rsrc = p.part + (int64_t)S * MN + row;
     float acc = rsrc[0];
     for (int s = 1; s < S; ++s) acc += rsrc[(int64_t)s * p.M];
-    apply_epilogue(p, row, p.ones_col, alpha * acc);
+    store_epilogue(p, row, p.ones_col, alpha, acc);
   }
 }
 
@@ -1041,7 +1020,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_generic_kernel(const GemmPar
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t row = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-    if (row < p.M && col < p.N) apply_epilogue(p, row, col, alpha * acc[r]);
+    if (row < p.M && col < p.N) store_epilogue(p, row, col, alpha, acc[r]);
   }
 }
 
@@ -1058,7 +1037,7 @@ __global__ __launch_bounds__(kThreads) void gemm_rowsum_kernel(const GemmParams 
   part[ks][r] = s;
   __syncthreads();
   if (ks == 0 && m < p.M)
-    apply_epilogue(p, m, p.ones_col, alpha * (((part[0][r] + part[1][r]) + part[2][r]) + part[3][r]));
+    store_epilogue(p, m, p.ones_col, alpha, ((part[0][r] + part[1][r]) + part[2][r]) + part[3][r]);
 }
 
 // ------------------------------------------------------------------- planning --

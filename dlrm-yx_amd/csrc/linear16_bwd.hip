@@ -204,7 +204,10 @@ __global__ __launch_bounds__(kThreads) void linear16_bwd_kernel(const BwdArgs p)
         if (p.epi == kEpiDgrad) {
           if (p.mask) v = p.mask[ci * p.ldmask + cj] > 0.f ? v : 0.f;  // selects, NaN -> 0
         } else if (p.epi == kEpiSgd) {
-          v = __fsub_rn(*o, __fmul_rn(lr, v));  // two roundings, as DLRM_EPI_SGD
+          // ONE rounding, unlike DLRM_EPI_SGD: the __fsub_rn(*o, __fmul_rn(lr, v)) that stood
+          // here always compiled to this fma (common.hpp, dlrm_scale), and the bf16 step
+          // traces pin its bits.  Two roundings are dlrm_sgd_step(*o, dlrm_scale(lr, v)).
+          v = fmaf(-lr, v, *o);
         }
         *o = v;
       }
@@ -222,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void wgrad16_reduce_kernel(
   float acc = partial[idx];
   for (int s = 1; s < splits; ++s) acc += partial[int64_t(s) * N * K + idx];
   float* o = C + (idx / K) * ldc + idx % K;
-  *o = sgd ? __fsub_rn(*o, __fmul_rn(lr, acc)) : acc;
+  *o = sgd ? fmaf(-lr, acc, *o) : acc;  // one rounding, as the unsplit epilogue above
 }
 
 template <typename T, int BM, int BN, bool TRANS_A>

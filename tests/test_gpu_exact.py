@@ -415,6 +415,215 @@ def test_gemm_empty_output_is_a_no_op(ops, M, N):
     assert int(ws.view(torch.int64).abs().sum()) == 0
 
 
+# -------------------------------------------------------------- g. epilogue rounding --
+# The epilogue is TWO roundings, fl(old -+ fl(alpha * acc)) and fl(fl(alpha * acc) + bias)
+# (common.hpp dlrm_scale, then one rounded add or subtract), on every output path.  The
+# integer cases above cannot tell that from one fused multiply-add: every rounding is exact
+# for them.  Here op(A) is one-hot and op(B) full-mantissa (section b: every accumulator is
+# one correctly rounded product, every row sum the row's single nonzero, a K split adds exact
+# zeros), alpha is fp32(0.7) and the old C and the bias are full-mantissa with random signs,
+# so the fused result differs from the two-rounding one in a large share of the elements -
+# asserted before anything runs.  All references are float64 on the CPU: alpha * acc of two
+# fp32 values has 48 significant bits and is exact there, and so is its sum with a third fp32
+# value of a similar exponent, so each .float() below is exactly one fp32 rounding.
+ALPHA_R = float(np.float32(0.7))  # not a "round" rate: at 0.1 only 5 % of the elements differ
+
+
+def _signed_mantissas(shape, g):
+    sign = torch.randint(0, 2, shape, generator=g, device=g.device).float() * 2 - 1
+    return full_mantissa(shape, g) * sign
+
+
+def _two_and_fused(epi_name, acc64, old64, bias64, alpha=ALPHA_R):
+    """(two, fused) as fp32: the two-rounding epilogue and the single fused multiply-add."""
+    prod = alpha * acc64                  # exact in float64
+    scaled = prod.float().double()        # fl(alpha * acc)
+    if epi_name == "sgd":
+        return (old64 - scaled).float(), (old64 - prod).float()
+    if epi_name == "accum":
+        return (old64 + scaled).float(), (old64 + prod).float()
+    assert epi_name == "bias"
+    return (scaled + bias64).float(), (prod + bias64).float()
+
+
+class RoundingCase:
+    """One-hot op(A) [M, K] x full-mantissa op(B) [K, N] in layout (ta, tb), the old C
+    [M, N + 4] (column N takes the row sums of a ones_col problem) and a bias; built once per
+    (M, layout) and shared - the kernels only read it."""
+
+    def __init__(self, ta, tb, M, N=96, K=512, seed=7):
+        self.M, self.N, self.ta, self.tb = M, N, ta, tb
+        self.A, self.B, acc = _one_hot_pair(ta, tb, False, M, N, K, seed)
+        g = _gen(4000 + 16 * seed + 2 * ta + tb + 8 * M)
+        self.C0 = _signed_mantissas((M, N + 4), g)
+        self.bias = _nan_vector(_signed_mantissas((N,), g))
+        opA = self.A.t() if ta else self.A
+        self.rowsum64 = opA.double().sum(1).cpu()  # one nonzero per row: exact
+        assert int((opA != 0).sum(1).max()) == 1
+        self.acc64 = acc.double().cpu()
+
+    def references(self, epi_name, ones):
+        """(two, fused, old) over the written width: N, or N + 1 with the row-sum column."""
+        acc = self.acc64
+        if ones:
+            assert epi_name != "bias"  # no bias column
+            acc = torch.cat([acc, self.rowsum64[:, None]], 1)
+        w = acc.shape[1]
+        old = self.C0.cpu()
+        bias = self.bias.double().cpu() if epi_name == "bias" else None
+        two, fused = _two_and_fused(epi_name, acc, old[:, :w].double(), bias)
+        return two, fused, old
+
+    def condition(self, epi_name, ones, min_rowsums=None):
+        """two != fused in >= 25 % of the M x N block and >= 10 % of the ones_col column (or
+        ``min_rowsums`` of its elements, for a small M)."""
+        two, fused, _ = self.references(epi_name, ones)
+        d = two != fused
+        share = float(d[:, :self.N].float().mean())
+        assert share >= 0.25, (epi_name, share)
+        if ones:
+            n = int(d[:, self.N].sum())
+            need = min_rowsums if min_rowsums is not None else 0.10 * self.M
+            assert n >= need, (epi_name, "row sums", n, self.M)
+
+    def output(self, ones):
+        return padded(self.C0 if ones else self.C0[:, :self.N], 2, 4, SENTINEL)
+
+    def problem(self, ops, C, epi_name, ones, A=None, **kw):
+        epi = {"sgd": ops.EPI_SGD, "accum": ops.EPI_ACCUM, "bias": ops.EPI_BIAS}[epi_name]
+        A = padded(self.A, 2, 4, NAN) if A is None else A
+        return ops.gemm_problem(A, padded(self.B, 2, 4, NAN), bool(self.ta), bool(self.tb), C=C,
+                                alpha=ALPHA_R, epilogue=epi, bias=self.bias,
+                                ones_col=self.N if ones else -1, **kw)[0]
+
+    def check(self, C, epi_name, ones, what=()):
+        """C equals the two-rounding reference bitwise; its other columns keep the old C."""
+        two, fused, old = self.references(epi_name, ones)
+        ref = old[:, :C.shape[1]].clone()
+        ref[:, :two.shape[1]] = two
+        got = C.cpu()
+        tag = (self.M, self.ta, self.tb, epi_name, ones) + tuple(what)
+        if not torch.equal(got, ref):
+            as_fused = int(((got[:, :two.shape[1]] == fused) & (two != fused)).sum())
+            raise AssertionError((tag, _first_diff(got, ref),
+                                  f"{as_fused} of {int((two != fused).sum())} elements that "
+                                  f"can tell hold the FUSED result"))
+
+    def run_and_check(self, ops, ws, epi_name, ones, what=(), A=None):
+        C = self.output(ones)
+        ops.gemm_group([self.problem(ops, C, epi_name, ones, A=A)], ws)
+        self.check(C, epi_name, ones, what)
+        assert pads_intact(C), what
+
+
+# (layout, epilogue, ones_col): the forward with its bias, the wgrad with the fused update
+ROUNDING_KINDS = [((0, 1), "bias", False), ((1, 0), "sgd", True), ((1, 0), "accum", True)]
+
+
+@functools.lru_cache(maxsize=None)
+def _rounding_case(ta, tb, M=128):
+    return RoundingCase(ta, tb, M)
+
+
+def _rounding_cases(M=128, kinds=ROUNDING_KINDS, min_rowsums=None):
+    out = []
+    for (ta, tb), epi_name, ones in kinds:
+        c = _rounding_case(ta, tb, M)
+        c.condition(epi_name, ones, min_rowsums)
+        out.append((c, epi_name, ones))
+    return out
+
+
+@pytest.mark.parametrize("cfg", GEMM_CFGS)
+def test_gemm_rounding_pipelined(ops, cfg):
+    """The batched epilogue of the pipelined body: every tile, unsplit and split 4, the
+    forward layout with EPI_BIAS and the wgrad layout with EPI_SGD and EPI_ACCUM and the
+    ones_col row sums - each element the two-rounding result, bitwise."""
+    cases = _rounding_cases()
+    ws = _workspace()
+    for split in (1, 4):
+        for c, epi_name, ones in cases:
+            with ops.tuning(gemm_tile=cfg, gemm_split=split):
+                c.run_and_check(ops, ws, epi_name, ones, what=(cfg, split))
+    assert _tickets_zero(ws)
+
+
+def test_gemm_rounding_64bit_epilogue(ops):
+    """finish_tile's 64-bit fallback: the same problem at M = 16 with C a strided view whose
+    rows lie 1 972 832 floats apart, so (M + 256) * ldc * 4 passes the 32-bit offset limit
+    and the batched epilogue is not taken.  EPI_SGD with the row sums and EPI_BIAS, unsplit
+    and split 4 on the default tile; every other float of the buffer keeps its sentinel."""
+    M, ldc = 16, 1_972_832
+    cases = _rounding_cases(M, [ROUNDING_KINDS[1], ROUNDING_KINDS[0]], min_rowsums=2)
+    ws = _workspace()
+    buf = torch.full((M * ldc,), SENTINEL, device=dev)
+    for split in (1, 4):
+        for c, epi_name, ones in cases:
+            w = c.N + 4 if ones else c.N
+            C = buf.as_strided((M, w), (ldc, 1))
+            assert C.stride(0) == ldc and C.data_ptr() == buf.data_ptr()
+            assert (M + 256) * C.stride(0) * 4 >= 0x7ff00000  # gemm.hip epi_fits: false
+            C.copy_(c.C0[:, :w])
+            with ops.tuning(gemm_split=split):
+                ops.gemm_group([c.problem(ops, C, epi_name, ones)], ws)
+            c.check(C, epi_name, ones, what=("64-bit", split))
+            C.fill_(SENTINEL)  # what is left must be the untouched fill, bit for bit
+            assert bool((buf.view(torch.int32) ==
+                         torch.tensor(SENTINEL).view(torch.int32).item()).all()), (epi_name, split)
+    assert _tickets_zero(ws)
+
+
+@pytest.mark.parametrize("epi_name", ["sgd", "accum"])
+@pytest.mark.parametrize("requested", [1, 3])
+def test_gemm_rounding_partial_then_reduce(ops, epi_name, requested):
+    """PARTIAL, then the REDUCE job of a later launch: the weight columns (the float4 path)
+    and the bias column (one element per thread) both hold the two-rounding result, hence
+    agree with each other."""
+    (c, _, ones), = _rounding_cases(kinds=[((1, 0), epi_name, True)])
+    ws = _workspace()
+    C = c.output(ones)
+    s = ops.gemm_splits(c.problem(ops, C, epi_name, ones), partial=True, requested=requested)
+    assert s == _normalized_splits(requested, 512)
+    part = torch.full((ops.gemm_partial_bytes(c.M, c.N, s) // 4,), NAN, device=dev)
+    pp = c.problem(ops, C, epi_name, ones, partial=part, splits=s)
+    ops.gemm_group([pp], ws)
+    assert torch.equal(C, c.C0)  # PARTIAL leaves C alone
+    ops.gemm_group([ops.reduce_problem(pp)], ws)
+    c.check(C, epi_name, ones, what=("reduce", requested))
+    assert pads_intact(C)
+    assert _tickets_zero(ws)
+
+
+def test_gemm_rounding_generic_and_rowsum_kernels(ops):
+    """The element-guarded fallback and its row-sum kernel (A one float off 16-byte
+    alignment): EPI_SGD with ones_col, and EPI_BIAS."""
+    ws = _workspace()
+    for c, epi_name, ones in _rounding_cases(kinds=[ROUNDING_KINDS[1], ROUNDING_KINDS[0]]):
+        c.run_and_check(ops, ws, epi_name, ones, what=("generic",),
+                        A=_offset_by_one_float(c.A, 2, 4))
+    assert _tickets_zero(ws)
+
+
+def test_gemm_rounding_sgd_job(ops):
+    """ops.sgd_job alone in a launch on flat full-mantissa p and g: fl(p - fl(lr * g)), not
+    the fused multiply-add; nothing past the parameter is written."""
+    ws = _workspace()
+    g = _gen(53)
+    n = 4100
+    p0, grad = _signed_mantissas((n,), g), _signed_mantissas((n,), g)
+    two, fused = _two_and_fused("sgd", grad.double().cpu(), p0.double().cpu(), None)
+    assert float((two != fused).float().mean()) >= 0.25
+    buf = torch.full((n + 64,), SENTINEL, device=dev)
+    p = buf[:n]
+    p.copy_(p0)
+    ops.gemm_group([ops.sgd_job(p, grad, ALPHA_R)], ws)
+    got = p.cpu()
+    assert torch.equal(got, two), (_first_diff(got, two),
+                                   int(((got == fused) & (two != fused)).sum()), "hold fused")
+    assert bool((buf[n:] == SENTINEL).all())
+    assert _tickets_zero(ws)
+
+
 # ------------------------------------------------------------ bottom-MLP chain --
 def _pad4(n):
     return (n + 3) // 4 * 4
