@@ -728,6 +728,52 @@ def interact_forward_gather_rows(x: torch.Tensor, packed: torch.Tensor, fmt: int
     return out
 
 
+def interact_forward_pool(x: torch.Tensor, weights: torch.Tensor, fmt: int, D: int,
+                          row_base: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor,
+                          self_interaction: bool = False, out: Optional[torch.Tensor] = None,
+                          pooled_out: Optional[torch.Tensor] = None,
+                          error_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dot interaction of x and the pooled multi-hot lookups of T = len(row_base) - 1 tables
+    (dlrm_interact_dot_forward_pool): the same R as interact_forward(x, tbe_forward(...)) in one
+    launch, the bags (``indices`` / ``offsets``: tbe_forward's int32 table-batched CSR, any
+    bag length) summed in registers straight from ``weights``.  ``fmt`` ROWS_F32 | ROWS_F16:
+    contiguous [rows, D] fp32 | fp16; ROWS_Q8 | ROWS_Q4: contiguous uint8 [rows, row_bytes]
+    (rows_quantize's output).  ``pooled_out``: a [B, T, D] fp32 tensor (any batch stride) that
+    also receives the pooled features, bitwise tbe_forward's / tbe_forward_rows'.  No
+    per-sample weights."""
+    _check_cuda(x, weights, row_base, indices, offsets, pooled_out)
+    want = {ROWS_F32: torch.float32, ROWS_F16: torch.float16, ROWS_Q8: torch.uint8,
+            ROWS_Q4: torch.uint8}.get(fmt)
+    if want is None:
+        raise ValueError(f"pooled interaction: unknown row format {fmt!r}")
+    if weights.dtype != want or weights.dim() != 2 or not weights.is_contiguous():
+        raise ValueError(f"pooled interaction: format {fmt} takes contiguous 2-D {want} rows, "
+                         f"not {weights.dtype} {tuple(weights.shape)}")
+    if fmt in (ROWS_F32, ROWS_F16) and weights.shape[1] != D:
+        raise ValueError(f"pooled interaction: rows are [rows, {D}], not {tuple(weights.shape)}")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != D or x.stride(1) != 1:
+        raise ValueError(f"pooled interaction: x is fp32 [B, {D}]")
+    B = x.shape[0]
+    F = row_base.numel()
+    npairs = F * (F + 1) // 2 if self_interaction else F * (F - 1) // 2
+    if indices.dtype != torch.int32 or offsets.dtype != torch.int32 \
+            or offsets.numel() != (F - 1) * B + 1:
+        raise ValueError("pooled interaction: int32 indices and int32 offsets [(F-1) * B + 1]")
+    if pooled_out is not None and (pooled_out.dtype != torch.float32
+                                   or tuple(pooled_out.shape) != (B, F - 1, D)
+                                   or pooled_out.stride()[1:] != (D, 1)):
+        raise ValueError(f"pooled interaction: pooled_out is fp32 [{B}, {F - 1}, {D}] with "
+                         "contiguous features")
+    if out is None:
+        out = torch.empty(B, D + npairs, dtype=torch.float32, device=x.device)
+    _lib.call("dlrm_interact_dot_forward_pool", B, F, D, _p(x), x.stride(0), _p(weights),
+              int(fmt), weights.stride(0) * weights.element_size(), _p(row_base), _p(indices),
+              _p(offsets), int(self_interaction), _p(out), out.stride(0), _p(pooled_out),
+              pooled_out.stride(0) if pooled_out is not None else 0, _p(error_flag),
+              _stream(x.device))
+    return out
+
+
 def interact_backward_gather(x: torch.Tensor, weights: torch.Tensor, row_base: torch.Tensor,
                              indices: torch.Tensor, grad_out: torch.Tensor,
                              self_interaction: bool = False,

@@ -367,6 +367,12 @@ class DLRMTrainer:
         # the overlap recovers at C3 (profiles/r01_overlap_ab.txt).
         self.overlaps = set()
         self._side = torch.cuda.Stream(device=self.dev)
+        # one-GPU graphs are captured on a stream of the trainer's own, drawn right after the
+        # side stream.  torch deals streams round-robin from a pool of 32 and its default
+        # capture stream is one of them, so about every 32nd trainer of a process got a side
+        # stream that WAS the capture stream: its captured step then forked onto the stream it
+        # was already on (the early sort and the overlaps ran in line, not beside the step)
+        self._capture_stream = torch.cuda.Stream(device=self.dev)
         self._tbe_ws: Optional[torch.Tensor] = None
         # run the embedding backward's per-table sort inside the lookup launch
         # (dlrm_tbe_forward_presort); False: the backward sorts itself
@@ -423,6 +429,12 @@ class DLRMTrainer:
         self.tbe_role_at = (0, 1)  # bottom-backward launches carrying pass 1 and pass 2
         self._roles = []  # pending (role, phase) passes for the step's next GEMM launches
         self.gather_fused = False  # set by the last step
+        # one GPU, multi-hot batches: the dot interaction pools the bags itself
+        # (dlrm_interact_dot_forward_pool); the lookup launch keeps its sort and
+        # bottom-MLP roles and the pooled [B, T, D] buffer is written only for the backward.
+        # Off by default: batches that are not one-hot keep the two launches
+        self.fuse_pool = False
+        self.pool_fused = False  # set by the last step
         self.bottom_fused = False  # set by the last step
         # device TBE error bits (ops.TBE_ERR_*): out-of-range indices are skipped by the
         # kernels and flagged here; check_errors() reads it (the step never syncs)
@@ -900,6 +912,8 @@ class DLRMTrainer:
         # the forward-only pass runs dlrm_tbe_forward: nothing of the backward's sort
         presort = train and self.tbe_presort
         gather = (presort or not train) and not dist and self._gather_applies(batch)
+        # multi-hot batches: the bags pooled inside the interaction instead (fuse_pool)
+        pool = (presort or not train) and not dist and not gather and self._pool_applies(batch)
         # fp16 tables (cfg.emb_precision): the same pieces on the fp16 row buffer - the
         # gather-fused interaction reads half rows, the pooled lookup is dlrm_tbe_forward_rows
         # and the update MODE_SGD_F16 as launches of its own (no fp16 launch role: tbe_role
@@ -928,6 +942,7 @@ class DLRMTrainer:
         if train:
             self._cur = bufs
             self.gather_fused = gather
+            self.pool_fused = pool
             ws, ws_keys = bufs, ("gemm_ws", "gemm_ws_side")
         else:
             # its own outputs and GEMM workspaces: it never touches self._cur, self._roles,
@@ -996,7 +1011,20 @@ class DLRMTrainer:
                     st["csr"] = self._phys_csr(batch, B)
                 idx, off = st["csr"]
                 out = bufs["P"] if self.qr_active else bufs["E"]
-                if qrows is not None:  # forward only, never with QR: one pooled Q lookup
+                if pool:
+                    # the interaction pools the bags: the lookup launch keeps its sort role
+                    # and the bottom MLP's where the per-table sort applies, else the backward
+                    # sorts itself (predict never gets here)
+                    st["presorted"] = self._presort_sorts(batch, idx, B)
+                    if st["presorted"]:
+                        ops.tbe_forward_presort(self.weights, self.row_base, self.T_phys, B,
+                                                idx, off, self._ws_tbe(idx.numel()),
+                                                batch.max_per_table,
+                                                error_flag=self.tbe_error_flag, bottom=bottom,
+                                                lookup=False)
+                    elif bottom is not None:
+                        ops.mlp_chain_forward(bottom, self.dev)
+                elif qrows is not None:  # forward only, never with QR: one pooled Q lookup
                     ops.tbe_forward_rows(qrows, qfmt, D, self.row_base, self.T_phys, B, idx,
                                          off, out=out, out_batch_stride=out.stride(0),
                                          error_flag=self.tbe_error_flag)
@@ -1069,6 +1097,15 @@ class DLRMTrainer:
                     ops.interact_forward_gather_rows(x, qrows, qfmt, D, self.row_base,
                                                      batch.indices, cfg.arch_interaction_itself,
                                                      out=bufs["R"], error_flag=self.tbe_error_flag)
+                elif pool:  # multi-hot lookup fused: bags pooled in registers; a training
+                    # step keeps the pooled features for the backward
+                    w, fmt = (qrows, qfmt) if qrows is not None else \
+                        (self.weights, ops.ROWS_F16 if f16 else ops.ROWS_F32)
+                    ops.interact_forward_pool(x, w, fmt, D, self.row_base, batch.indices,
+                                              batch.offsets, cfg.arch_interaction_itself,
+                                              out=bufs["R"],
+                                              pooled_out=bufs["E"] if train else None,
+                                              error_flag=self.tbe_error_flag)
                 elif gather:  # one-hot lookup fused: rows read straight from the tables
                     ops.interact_forward_gather(x, self.weights, self.row_base, batch.indices,
                                                 cfg.arch_interaction_itself, out=bufs["R"],
@@ -1093,7 +1130,7 @@ class DLRMTrainer:
 
         if not train:
             def lookup_only():  # no launch when the interaction gathers the rows itself
-                if self.T_local == 0 or gather:
+                if self.T_local == 0 or gather or pool:
                     return _EMPTY
                 st.pop("csr", None)  # QR: every run expands the batch's current contents
                 lookup()
@@ -1586,6 +1623,15 @@ class DLRMTrainer:
                 and self.weights.shape[0] < 0xFFFFFFFF
                 and batch.indices.numel() == self.T * batch.X.shape[0])
 
+    def _pool_applies(self, batch: Batch) -> bool:
+        """Multi-hot lookups pooled inside the dot interaction (fuse_pool): one GPU, plain
+        tables, a batch that is not one-hot, int32 CSR, D and F within the kernel's range."""
+        return (self.fuse_pool and not batch.one_hot and not self.distributed
+                and not self.qr_active and self.cfg.arch_interaction_op == "dot"
+                and self.D in (16, 32, 64, 128) and 1 <= self.T_local == self.T
+                and self.T + 1 <= 32 and batch.indices.dtype == torch.int32
+                and batch.offsets.dtype == torch.int32)
+
     def _presort_sorts(self, batch: Batch, idx: torch.Tensor, B: int) -> bool:
         """Whether the lookup launch runs the backward's per-table sort for this batch
         (dlrm_tbe_forward_presort's own rule: 32-bit row keys, every table within the LDS
@@ -1631,6 +1677,11 @@ class DLRMTrainer:
             lambda: self.segments(batch), pool, whole)
         return run
 
+    def _graph_stream(self):
+        """The stream graphs are captured on: the trainer's own on one GPU (never its side
+        stream), torch's default (None) with collectives in the step."""
+        return None if self.distributed else self._capture_stream
+
     def _capture_segments(self, make_segs, pool, whole):
         """capture()'s two modes over any segment list (``make_segs()`` builds a fresh one:
         the training step's or predict_segments').  Returns (callable, mode, graphs per
@@ -1643,7 +1694,7 @@ class DLRMTrainer:
             host = [fn for kind, fn in segs if kind == "host"]
             g = torch.cuda.CUDAGraph()
             try:
-                with torch.cuda.graph(g, pool=pool):
+                with torch.cuda.graph(g, pool=pool, stream=self._graph_stream()):
                     for kind, fn in segs:
                         if kind != "host":
                             fn()
@@ -1673,7 +1724,7 @@ class DLRMTrainer:
             if not pending:
                 return
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
+            with torch.cuda.graph(g, pool=pool, stream=self._graph_stream()):
                 launched = [fn() is not _EMPTY for fn in pending]
             if any(launched):  # a segment that enqueued nothing is not replayed
                 items.append(g.replay)
@@ -1899,7 +1950,8 @@ class DLRMTrainer:
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
-                   self._gather_applies(batch), precision, emb_bits, mlp_bits)
+                   self._gather_applies(batch), self._pool_applies(batch), precision, emb_bits,
+                   mlp_bits)
             if key not in graphs:
                 fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
                               batch.target.clone(), batch.max_per_table, batch.one_hot)

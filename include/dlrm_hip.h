@@ -145,8 +145,11 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    torch.quantization.quantize_dynamic's fbgemm arithmetic + DLRM_TUNE_LINEAR8_TILE.
  * 19: element-wise Adagrad fused into the embedding backward: dlrm_tbe_backward_adagrad
  *    (torch.optim.Adagrad's sparse step on a [total_rows, D] fp32 accumulator, host or
- *    device rate). */
-#define DLRM_ABI_VERSION 19/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    device rate).
+ * 20: the multi-hot lookup fused into the dot interaction: dlrm_interact_dot_forward_pool
+ *    (bags of any length pooled in registers from fp32 / fp16 / Q8 / Q4 rows, then the Gram
+ *    product; the pooled [B, T, D] buffer written only on request). */
+#define DLRM_ABI_VERSION 20/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -614,6 +617,34 @@ int dlrm_interact_dot_forward_gather_rows(int32_t B, int32_t F, int32_t D, const
                                           const int32_t* indices, int32_t self_interaction,
                                           float* out, int64_t ld_out, int32_t* error_flag,
                                           dlrm_stream_t stream);
+/*
+ * ABI v20.  The multi-hot lookup fused into the dot interaction (one GPU; apply_emb with any
+ * bag length, dlrm_s_pytorch.py:526-587, then interact_features :627-659) in one launch:
+ * feature 0 is x, feature f >= 1 of sample b is the sum of the rows
+ * row_base[f-1] + indices[l], offsets[(f-1)*B + b] <= l < offsets[(f-1)*B + b + 1], of
+ * `weights`: the table-batched CSR of dlrm_tbe_forward (bag (t, b) = t*B + b, `offsets` has
+ * (F-1)*B + 1 entries), int32.  `weights` is [total rows][row_bytes] in any dlrm_rows_format
+ * (other values: UNSUPPORTED), row_bytes == 4 D for DLRM_ROWS_F32 and
+ * dlrm_tbe_row_bytes(format, D) otherwise (else INVALID_ARG), 16-byte aligned (DLRM_ROWS_F16:
+ * 8).  The pooled value is bitwise dlrm_tbe_forward's / dlrm_tbe_forward_rows' (accumulated
+ * from 0 in lookup order: acc + row for fp32 and fp16 rows, fmaf(scale, q, acc + bias) for
+ * Q8 / Q4), an empty bag pools to zeros, and an index outside its table is dropped from its
+ * bag and sets DLRM_TBE_ERR_INDEX in *error_flag (may be NULL).  `out` as
+ * dlrm_interact_dot_forward, with the arithmetic of its LDS-staged kernel (the one it runs at
+ * B > 1024 or D < 64).  pooled_out (may be NULL): the pooled features are also written to
+ * pooled_out[b*pooled_bstride + (f-1)*D ...] (16-byte aligned, pooled_bstride % 4 == 0), e.g.
+ * the [B, T, D] buffer dlrm_interact_dot_backward reads.  D in {16, 32, 64, 128},
+ * 2 <= F <= 32; B == 0 launches nothing.  No allocation and no synchronisation: the call can
+ * be captured.  Per-sample weights are not supported (the fused engine has no weighted
+ * pooling): weighted bags keep dlrm_tbe_forward + dlrm_interact_dot_forward.
+ */
+int dlrm_interact_dot_forward_pool(int32_t B, int32_t F, int32_t D, const float* x,
+                                   int64_t x_bstride, const void* weights, int32_t format,
+                                   int64_t row_bytes, const int64_t* row_base,
+                                   const int32_t* indices, const int32_t* offsets,
+                                   int32_t self_interaction, float* out, int64_t ld_out,
+                                   float* pooled_out, int64_t pooled_bstride,
+                                   int32_t* error_flag, dlrm_stream_t stream);
 /* Cat: out[b][f*D:(f+1)*D] = feature f. */
 int dlrm_interact_cat_forward(int32_t B, int32_t F, int32_t D, const float* const* feat_ptrs,
                               const int64_t* feat_bstrides, float* out, int64_t ld_out,
