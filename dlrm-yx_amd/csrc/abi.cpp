@@ -21,9 +21,9 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
-// ABI v17 - v20: the version is only reported by a library that links the entry points it names
+// ABI v17 - v21: the version is only reported by a library that links the entry points it names
 // (taking their addresses with the header's types fails the build if one is missing).
-static_assert(DLRM_ABI_VERSION >= 20, "abi.cpp checks the v17 - v20 entry points");
+static_assert(DLRM_ABI_VERSION >= 21, "abi.cpp checks the v17 - v21 entry points");
 namespace {
 [[maybe_unused]] int (*const kLinear8Pack)(int64_t, int64_t, const float*, int64_t, int8_t*,
                                            int64_t, float*, void*, size_t,
@@ -51,6 +51,10 @@ namespace {
                                            const int32_t*, const int32_t*, int32_t, float*,
                                            int64_t, float*, int64_t, int32_t*,
                                            dlrm_stream_t) = &dlrm_interact_dot_forward_pool;
+[[maybe_unused]] int (*const kChain16Supported)(const dlrm_mlp_chain16*) =
+    &dlrm_mlp_chain16_supported;
+[[maybe_unused]] int (*const kChain16Forward)(const dlrm_mlp_chain16*,
+                                              dlrm_stream_t) = &dlrm_mlp_chain16_forward;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 20
+ABI_VERSION = 21
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -49,6 +49,16 @@ class MlpChain(ctypes.Structure):
                 ("W", c_void_p * MLP_MAX_LAYERS), ("ldw", c_int64 * MLP_MAX_LAYERS),
                 ("Y", c_void_p * MLP_MAX_LAYERS), ("ldy", c_int64 * MLP_MAX_LAYERS),
                 ("parts", c_int32), ("split_layer", c_int32), ("tickets", c_void_p)]
+
+
+class MlpChain16(ctypes.Structure):
+    """struct dlrm_mlp_chain16 (include/dlrm_hip.h)."""
+    _fields_ = [("type", c_int32), ("layers", c_int32), ("rows", c_int64), ("X", c_void_p),
+                ("ldx", c_int64), ("in_width", c_int64),
+                ("out_width", c_int64 * MLP_MAX_LAYERS),
+                ("W", c_void_p * MLP_MAX_LAYERS), ("ldw", c_int64 * MLP_MAX_LAYERS),
+                ("bias", c_void_p * MLP_MAX_LAYERS), ("bias_stride", c_int64 * MLP_MAX_LAYERS),
+                ("Y", c_void_p * MLP_MAX_LAYERS), ("ldy", c_int64 * MLP_MAX_LAYERS)]
 
 
 # name -> (restype, argtypes); mirrors include/dlrm_hip.h exactly.
@@ -237,6 +247,9 @@ SIGNATURES = {
     "dlrm_interact_dot_forward_pool": (c_int32, [c_int32, c_int32, c_int32, P, c_int64, P,
                                                  c_int32, c_int64, P, P, P, c_int32, P, c_int64,
                                                  P, c_int64, P, P]),
+    # ABI v21: the 16-bit bottom-MLP chain (every layer on the bf16 / fp16 MFMA in one launch)
+    "dlrm_mlp_chain16_supported": (c_int32, [P]),
+    "dlrm_mlp_chain16_forward": (c_int32, [P, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

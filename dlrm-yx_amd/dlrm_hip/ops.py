@@ -1059,6 +1059,60 @@ def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tens
     return out
 
 
+def mlp_chain16(X: torch.Tensor, layers, dtype: str = "bf16") -> "_lib.MlpChain16":
+    """dlrm_mlp_chain16 for a Linear+ReLU stack on the 16-bit MFMA: ``X`` [rows, K_0] and
+    ``layers`` = [(W [N, K], bias [N] or None, Y [rows, N] or None)], fp32 tensors or views with
+    contiguous rows as linear16_forward takes them (K of a layer is the N of the one before;
+    ``bias`` may be a strided column of W's buffer).  Y = None: that layer's activations are
+    not written (they stay in LDS); the last layer's Y is required.  Every check runs here,
+    before the library is loaded."""
+    fn = "mlp_chain16"
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"{fn}: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    layers = list(layers)
+    if not layers:
+        raise ValueError(f"{fn}: no layers")
+    if layers[-1][2] is None:
+        raise ValueError(f"{fn}: the last layer's Y is required")
+    c = _lib.MlpChain16()
+    c.type, c.layers = MLP16_TYPES[dtype], len(layers)
+    c.ldx = _row_major(X, "X", fn)
+    c.rows, c.in_width = X.shape
+    c.X = X.data_ptr()
+    K = X.shape[1]
+    for i, (W, bias, Y) in enumerate(layers[:_lib.MLP_MAX_LAYERS]):
+        ldw, N = _row_major(W, f"W[{i}]", fn), W.shape[0]
+        if W.shape[1] != K:
+            raise ValueError(f"{fn}: layer {i}'s input is {K} wide, W is {list(W.shape)}")
+        if bias is not None:
+            if bias.dim() != 1 or bias.numel() != N or bias.dtype != torch.float32:
+                raise ValueError(f"{fn}: bias[{i}] must be N = {N} fp32 values")
+            c.bias[i], c.bias_stride[i] = bias.data_ptr(), bias.stride(0) if N > 1 else 1
+        if Y is not None:
+            c.ldy[i] = _row_major(Y, f"Y[{i}]", fn)
+            if tuple(Y.shape) != (X.shape[0], N):
+                raise ValueError(f"{fn}: Y[{i}] is {list(Y.shape)}, expected [{X.shape[0]}, {N}]")
+            c.Y[i] = Y.data_ptr()
+        else:
+            c.ldy[i] = N
+        c.out_width[i], c.W[i], c.ldw[i] = N, W.data_ptr(), ldw
+        K = N
+    _check_cuda(X, *(t for layer in layers for t in layer))
+    c._keep = (X, layers)  # the struct refers to their memory
+    return c
+
+
+def mlp_chain16_supported(chain) -> bool:
+    return bool(_lib.load().dlrm_mlp_chain16_supported(ctypes.byref(chain)))
+
+
+def mlp_chain16_forward(chain, device=None) -> None:
+    """Every layer of the 16-bit chain in one launch (dlrm_mlp_chain16_forward)."""
+    dev = device if device is not None else torch.cuda.current_device()
+    _lib.call("dlrm_mlp_chain16_forward", ctypes.cast(ctypes.byref(chain), ctypes.c_void_p),
+              _stream(dev))
+
+
 LINEAR8_TILES = LINEAR16_TILES  # DLRM_TUNE_LINEAR8_TILE values
 LINEAR8_RANGE_FLOATS = 2048  # DLRM_LINEAR8_RANGE_FLOATS: min partials, then max partials
 LINEAR8_MAX_K = 131072

@@ -436,6 +436,13 @@ class DLRMTrainer:
         self.fuse_pool = False
         self.pool_fused = False  # set by the last step
         self.bottom_fused = False  # set by the last step
+        # 16-bit builds (predict / evaluate with precision "bf16" | "fp16", the training step of
+        # mlp_precision "bf16"): the bottom MLP as ONE dlrm_mlp_chain16 launch, activations
+        # rounded once into LDS, instead of a dlrm_linear16_forward per layer - the same bits
+        # (DESIGN.md §24).  A bottom MLP it does not take (a width above 512, more than 4
+        # layers) keeps the per-layer launches.  Off by default
+        self.fuse_bottom16 = False
+        self.bottom16_fused = False  # set by the last build (training step or predict)
         # device TBE error bits (ops.TBE_ERR_*): out-of-range indices are skipped by the
         # kernels and flagged here; check_errors() reads it (the step never syncs)
         self.tbe_error_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -927,8 +934,10 @@ class DLRMTrainer:
         # The 16-bit step has no launch role, no bottom chain in the lookup launch and no
         # side-stream overlap (DESIGN.md §16 has the plan to give it them): they are switched
         # off here, once, and the pieces below take the branches they take in an fp32 step
-        # with tbe_role, head_role, fuse_bottom and overlaps off.  The chain is an fp32
+        # with tbe_role, head_role, fuse_bottom and overlaps off.  That chain is an fp32
         # kernel, so a 16-bit predict does not use it either; it keeps the "fwd" overlap.
+        # The 16-bit chain (fuse_bottom16, below) is a launch of its own in place of the
+        # per-layer bottom launches, never a role of the lookup launch.
         plain = fp32 or not train
         overlaps = self.overlaps if plain and not dist else ()
         c_fwd = conc and "fwd" in overlaps
@@ -971,6 +980,11 @@ class DLRMTrainer:
 
         def chain(**kw):
             return self._bottom_chain(batch, bufs, **kw) if fuse_bottom else None
+
+        # a training step keeps every layer's activations for the backward; predict only the last
+        chain16 = self._bottom_chain16(batch, bufs, precision, keep=train) \
+            if self.fuse_bottom16 and not fp32 and q8 is None else None
+        self.bottom16_fused = chain16 is not None
 
         if fp32:
             def mlp_fwd(L, h, out, side=False):
@@ -1071,6 +1085,10 @@ class DLRMTrainer:
                 c = chain(sort_wgs=0, standalone=True) if own_chain else None
                 if c is not None:
                     ops.mlp_chain_forward(c, self.dev)
+                    return
+                if chain16 is not None:  # on the stream the per-layer loop would use
+                    with prof("gemm"):
+                        ops.mlp_chain16_forward(chain16, self.dev)
                     return
                 h = batch.X
                 for L, out in zip(self.bot, bufs["bot_act"]):
@@ -2057,6 +2075,16 @@ class DLRMTrainer:
                 return chain
         chain = ops.mlp_chain(batch.X, layers)
         return chain if ops.mlp_chain_supported(chain) else None
+
+    def _bottom_chain16(self, batch: Batch, bufs, precision: str, keep: bool):
+        """The bottom MLP forward of a 16-bit build as a dlrm_mlp_chain16 on the views the
+        per-layer launches take (None when the kernel does not support it).  ``keep``: every
+        layer's activations are written (the backward reads them), else only the last."""
+        last = len(self.bot) - 1
+        layers = [(L.W[:, :L.K], L.b, out[:, :L.N] if keep or i == last else None)
+                  for i, (L, out) in enumerate(zip(self.bot, bufs["bot_act"]))]
+        chain = ops.mlp_chain16(batch.X[:, :self.bot[0].K], layers, dtype=precision)
+        return chain if ops.mlp_chain16_supported(chain) else None
 
     def _ws_tbe(self, n: int) -> torch.Tensor:
         need = ops.tbe_backward_workspace_size(n, self.total_rows, self.D)

@@ -148,8 +148,12 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    device rate).
  * 20: the multi-hot lookup fused into the dot interaction: dlrm_interact_dot_forward_pool
  *    (bags of any length pooled in registers from fp32 / fp16 / Q8 / Q4 rows, then the Gram
- *    product; the pooled [B, T, D] buffer written only on request). */
-#define DLRM_ABI_VERSION 20/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    product; the pooled [B, T, D] buffer written only on request).
+ * 21: the 16-bit bottom-MLP chain: dlrm_mlp_chain16 / dlrm_mlp_chain16_supported /
+ *    dlrm_mlp_chain16_forward (up to four Linear+ReLU layers on the bf16 / fp16 MFMA in one
+ *    launch, the activations rounded once into LDS; the bits of dlrm_linear16_forward applied
+ *    layer by layer). */
+#define DLRM_ABI_VERSION 21/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -956,6 +960,51 @@ int dlrm_linear16_forward(int32_t type, int64_t M, int64_t N, int64_t K,
                           const float* X, int64_t ldx, const float* W, int64_t ldw,
                           const float* bias, int64_t bias_stride, /* NULL: none */
                           int32_t relu, float* Y, int64_t ldy, dlrm_stream_t stream);
+
+/*
+ * A Linear+ReLU stack on the 16-bit MFMA in ONE launch (ABI v21): for l < layers <= 4
+ *   Y_l[r][c] = relu( sum_{k < K_l} r16(In_l[r][k]) * r16(W_l[c][k]) + bias_l[c * bias_stride_l] )
+ * for c < out_width[l], with In_0 = X, K_0 = in_width and, for l > 0, In_l = Y_{l-1},
+ * K_l = out_width[l-1].  r16, the fp32 accumulation on v_mfma_f32_16x16x32_{bf16,f16}, the
+ * fp32 bias add (bias[l] == NULL: none) and the NaN-propagating fp32 ReLU are
+ * dlrm_linear16_forward's; X and every W_l stay fp32 in memory and are rounded in flight (no
+ * packed copy of the weights exists).  A workgroup owns 16 rows and keeps the activations in
+ * LDS as 16-bit values, rounded once when they are produced - the value the next per-layer
+ * call would round from the fp32 Y_l.
+ * Bit contract: every Y_l equals (==) what `layers` successive dlrm_linear16_forward calls
+ * (relu = 1) give on the same buffers: one accumulator chain per output element over the 32-k
+ * blocks in ascending order, the same operand-to-lane map, elements with k >= K_l selected to
+ * zero (never multiplied).  No split-K, no atomics, no workspace: two calls give the same bits.
+ * Only Y_l[0:rows][0:out_width[l]] is written, and not at all where Y[l] == NULL, which is
+ * allowed for l < layers - 1 (a forward-only pass needs no intermediates); the last layer's Y
+ * is required.  No element X[.][k >= in_width] or W_l[.][k >= K_l] is read (in the trainer's
+ * layout column K_l of W_l is the folded bias), whatever the leading dimensions; W_l takes
+ * 16-byte loads when it is 16-byte aligned and ldw[l] a multiple of 4, element loads
+ * otherwise.  Supported (dlrm_mlp_chain16_supported): 1..4 layers, 1 <= in_width <= 512,
+ * 1 <= out_width[l] <= 512, rows >= 0 (0: nothing to do) in fewer than 2^31 16-row blocks.
+ * An unknown type or a NULL required pointer is DLRM_ERR_INVALID_ARG, ldx < in_width,
+ * ldw[l] < K_l or ldy[l] < out_width[l] DLRM_ERR_SHAPE, a size outside the supported set
+ * DLRM_ERR_UNSUPPORTED (dlrm_last_error names it).
+ */
+typedef struct dlrm_mlp_chain16 {
+  int32_t type; /* dlrm_mlp16_type */
+  int32_t layers;
+  int64_t rows;
+  const float* X;
+  int64_t ldx;
+  int64_t in_width; /* K_0 */
+  int64_t out_width[DLRM_MLP_MAX_LAYERS]; /* N_l */
+  const float* W[DLRM_MLP_MAX_LAYERS];
+  int64_t ldw[DLRM_MLP_MAX_LAYERS];
+  const float* bias[DLRM_MLP_MAX_LAYERS]; /* NULL: none */
+  int64_t bias_stride[DLRM_MLP_MAX_LAYERS];
+  float* Y[DLRM_MLP_MAX_LAYERS]; /* NULL for l < layers - 1: not written */
+  int64_t ldy[DLRM_MLP_MAX_LAYERS];
+} dlrm_mlp_chain16;
+
+/* 1 when dlrm_mlp_chain16_forward can take this chain, else 0. */
+int dlrm_mlp_chain16_supported(const dlrm_mlp_chain16* chain);
+int dlrm_mlp_chain16_forward(const dlrm_mlp_chain16* chain, dlrm_stream_t stream);
 
 /* ---------------------------------------------------- int8 inference Linear -- */
 /*
