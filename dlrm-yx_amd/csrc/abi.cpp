@@ -21,9 +21,9 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
-// ABI v17 - v21: the version is only reported by a library that links the entry points it names
+// ABI v17 - v22: the version is only reported by a library that links the entry points it names
 // (taking their addresses with the header's types fails the build if one is missing).
-static_assert(DLRM_ABI_VERSION >= 21, "abi.cpp checks the v17 - v21 entry points");
+static_assert(DLRM_ABI_VERSION >= 22, "abi.cpp checks the v17 - v22 entry points");
 namespace {
 [[maybe_unused]] int (*const kLinear8Pack)(int64_t, int64_t, const float*, int64_t, int8_t*,
                                            int64_t, float*, void*, size_t,
@@ -55,6 +55,10 @@ namespace {
     &dlrm_mlp_chain16_supported;
 [[maybe_unused]] int (*const kChain16Forward)(const dlrm_mlp_chain16*,
                                               dlrm_stream_t) = &dlrm_mlp_chain16_forward;
+[[maybe_unused]] size_t (*const kBwd16GroupWs)(int32_t, int32_t, const dlrm_linear16_bwd_problem*) =
+    &dlrm_linear16_bwd_group_workspace_size;
+[[maybe_unused]] int (*const kBwd16Group)(int32_t, int32_t, const dlrm_linear16_bwd_problem*, void*,
+                                          size_t, dlrm_stream_t) = &dlrm_linear16_bwd_group;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

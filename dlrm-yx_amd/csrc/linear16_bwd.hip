@@ -23,197 +23,31 @@
 // split the reduction over `splits` workgroups per tile.  The partial tiles then go to the
 // workspace ([split][N][K] fp32) and a second launch sums them in split order and applies
 // STORE / SGD: no atomics, the same bits on every call.
-#include <type_traits>
-
-#include "linear16_stage.hpp"
+#include "linear16_bwd_tile.hpp"
 
 namespace dlrm {
 namespace {
 
 using namespace l16;
 
-constexpr int kMaxSplits = 32;
-
-// One thread's share of a [64 reduction rows][OUT columns] fp32 tile whose rows are
-// contiguous along the columns: RG reduction rows x 4 columns.
-template <int OUT>
-struct StageT {
-  static constexpr int kCG = OUT / 4;                  // groups of 4 columns
-  static constexpr int kRG = kBK / (kThreads / kCG);   // reduction rows per thread
-  static_assert(OUT == 32 || OUT == 64 || OUT == 128, "tile");
-  float v[kRG][4];
-
-  template <bool ALIGNED>
-  __device__ __forceinline__ void load(const float* __restrict__ P, int64_t ld, int64_t r0,
-                                       int64_t R, int64_t c0, int64_t C, int tid) {
-    const int64_t c = c0 + (tid % kCG) * 4;
-    const int64_t rb = r0 + (tid / kCG) * kRG;
-#pragma unroll
-    for (int i = 0; i < kRG; ++i) {
-      const int64_t r = rb + i;
-      if (r < R && c + 4 <= C) {
-        const float* p = P + r * ld + c;
-        if (ALIGNED) {
-          const float4 a = *reinterpret_cast<const float4*>(p);
-          v[i][0] = a.x, v[i][1] = a.y, v[i][2] = a.z, v[i][3] = a.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[i][j] = p[j];
-        }
-      } else if (r < R) {
-        const float* p = P + r * ld + c;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = (c + j < C) ? p[j] : 0.0f;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = 0.0f;  // a reduction tail: zero, nothing read
-      }
-    }
-  }
-
-  template <typename T>
-  __device__ __forceinline__ void store(typename Op16<T>::vec* lds, int tid) const {
-    typedef T packed __attribute__((ext_vector_type(kRG)));
-    T* base = reinterpret_cast<T*>(lds);
-    const int e = (tid / kCG) * kRG;  // first reduction element of this thread
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      packed h;
-#pragma unroll
-      for (int i = 0; i < kRG; ++i) h[i] = static_cast<T>(v[i][j]);  // RNE
-      const int row = (tid % kCG) * 4 + j;
-      *reinterpret_cast<packed*>(base + lds_chunk(row, e >> 3) * 8 + (e & 7)) = h;
-    }
-  }
-};
-
-enum Epi { kEpiDgrad = 0, kEpiStore = 1, kEpiSgd = 2, kEpiPartial = 3 };
-
-struct BwdArgs {
-  int64_t I, J, R;           // Out [I][J], reduction depth R
-  const float* A;            // TRANS_A ? [R][I] : [I][R]
-  int64_t lda;
-  const float* B;            // [R][J]
-  int64_t ldb;
-  const float* mask;         // kEpiDgrad: [I][J] or NULL
-  int64_t ldmask;
-  float* Out;                // kEpiPartial: the workspace, [split][I][J]
-  int64_t ldo;
-  int epi;
-  float lr;
-  const float* lr_dev;       // ABI v14: NULL, or the device fp32 that replaces lr (kEpiSgd)
-  int tiles_j, tiles;
-  int64_t steps_per_split;   // reduction steps of 64 per blockIdx.y
-};
-
+// the per-tile body (staging, LDS image, MFMA loop, epilogue) is linear16_bwd_tile.hpp's
 template <typename T, int BM, int BN, bool TRANS_A, bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void linear16_bwd_kernel(const BwdArgs p) {
   using vec = typename Op16<T>::vec;
-  constexpr int WTM = BM / 2, WTN = BN / 2;  // a wave's part of the tile
-  constexpr int FM = WTM / 16, FN = WTN / 16;
-  static_assert(BM % 32 == 0 && BN % 32 == 0, "tile");
-  __shared__ vec lds[2][(BM + BN) * 8];
+  __shared__ vec lds[2 * (BM + BN) * 8];
   const float lr = dlrm_resolve_lr(p.lr_dev, p.lr);
-
-  // consecutive tiles (j fastest: they share A) go to one XCD; bijective for any count
-  const int orig = blockIdx.x;
-  const int q = p.tiles / 8, rem = p.tiles % 8, xcd = orig % 8;
-  const int tile = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + orig / 8;
-  const int64_t i0 = int64_t(tile / p.tiles_j) * BM;
-  const int64_t j0 = int64_t(tile % p.tiles_j) * BN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = (wave >> 1) * WTM, wn = (wave & 1) * WTN;
-  const int fr = lane & 15, fc = lane >> 4;
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  typename std::conditional<TRANS_A, StageT<BM>, Stage<BM>>::type sa;
-  StageT<BN> sb;
-  const int64_t nk_all = (p.R + kBK - 1) / kBK;
-  const int64_t kt0 = int64_t(blockIdx.y) * p.steps_per_split;
-  const int64_t kt1 = kt0 + p.steps_per_split < nk_all ? kt0 + p.steps_per_split : nk_all;
-  auto fetch = [&](int64_t kt) {
-    const int64_t r0 = kt * kBK;
-    if constexpr (TRANS_A) {
-      sa.template load<ALIGNED>(p.A, p.lda, r0, p.R, i0, p.I, tid);
-    } else {
-      if (r0 + kBK <= p.R)
-        sa.template load<ALIGNED, true>(p.A, p.lda, i0, p.I, r0, p.R, tid);
-      else
-        sa.template load<ALIGNED, false>(p.A, p.lda, i0, p.I, r0, p.R, tid);
-    }
-    sb.template load<ALIGNED>(p.B, p.ldb, r0, p.R, j0, p.J, tid);
-  };
-  auto commit = [&](int buf) {
-    sa.template store<T>(lds[buf], tid);
-    sb.template store<T>(lds[buf] + BM * 8, tid);
-  };
-
-  if (kt0 < kt1) {
-    fetch(kt0);
-    commit(0);
-  }
-  __syncthreads();
-  for (int64_t kt = kt0; kt < kt1; ++kt) {
-    const int buf = int((kt - kt0) & 1);
-    if (kt + 1 < kt1) fetch(kt + 1);
-    const vec* A = lds[buf];
-    const vec* B = lds[buf] + BM * 8;
-#pragma unroll
-    for (int ks = 0; ks < kBK / 32; ++ks) {
-      vec a[FM], b[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) a[i] = A[lds_chunk(wm + i * 16 + fr, ks * 4 + fc)];
-#pragma unroll
-      for (int j = 0; j < FN; ++j) b[j] = B[lds_chunk(wn + j * 16 + fr, ks * 4 + fc)];
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = Op16<T>::mfma(a[i], b[j], acc[i][j]);
-    }
-    // the other buffer was last read in step kt - 1, which every wave left at its barrier
-    if (kt + 1 < kt1) commit(buf ^ 1);
-    __syncthreads();
-  }
-
-  // C/D map of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
+  f32x4 acc[BM / 32][BN / 32];
+  int64_t i0, j0;
+  bwd_tile_acc<T, BM, BN, TRANS_A, ALIGNED>(p, lds, blockIdx.x, blockIdx.y, acc, i0, j0);
   float* out = p.Out;
   int64_t ldo = p.ldo;
   if (p.epi == kEpiPartial) {
     out += int64_t(blockIdx.y) * p.I * p.J;
     ldo = p.J;
   }
-#pragma unroll
-  for (int j = 0; j < FN; ++j) {
-    const int64_t cj = j0 + wn + j * 16 + fr;
-    if (cj >= p.J) continue;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t ci = i0 + wm + i * 16 + fc * 4 + r;
-        if (ci >= p.I) continue;
-        float v = acc[i][j][r];
-        float* o = out + ci * ldo + cj;
-        if (p.epi == kEpiDgrad) {
-          if (p.mask) v = p.mask[ci * p.ldmask + cj] > 0.f ? v : 0.f;  // selects, NaN -> 0
-        } else if (p.epi == kEpiSgd) {
-          // ONE rounding, unlike DLRM_EPI_SGD: the __fsub_rn(*o, __fmul_rn(lr, v)) that stood
-          // here always compiled to this fma (common.hpp, dlrm_scale), and the bf16 step
-          // traces pin its bits.  Two roundings are dlrm_sgd_step(*o, dlrm_scale(lr, v)).
-          v = fmaf(-lr, v, *o);
-        }
-        *o = v;
-      }
-    }
-  }
+  bwd_tile_store<BM, BN>(p, p.epi, lr, acc, i0, j0, out, ldo);
 }
+
 
 // C[n][k] (op)= sum over the splits, in split order
 __global__ __launch_bounds__(kThreads) void wgrad16_reduce_kernel(
@@ -254,60 +88,6 @@ bool dispatch(Tile t, bool aligned, const BwdArgs& a, int splits, hipStream_t s)
   return false;
 }
 
-inline int64_t tiles_of(Tile t, int64_t I, int64_t J) {
-  return ceil_div(I, t.bm) * ceil_div(J, t.bn);
-}
-
-// dgrad: the forward's rule on the [M][K] output - the largest tile that still gives every CU
-// two workgroups, else the smallest.
-Tile plan_dgrad(int64_t I, int64_t J, int cus) {
-  for (const Tile& t : kTiles)
-    if (tiles_of(t, I, J) >= 2 * int64_t(cus)) return t;
-  return kTiles[kNumTiles - 1];
-}
-
-struct WgradPlan {
-  Tile tile;
-  int splits;
-  int64_t steps;  // reduction steps per split
-};
-
-// wgrad: 128 x 128 and no split where that tile alone gives every CU two workgroups.
-// Otherwise the tile by the number of 64 x 64 tiles of the [N][K] output (more than cus / 2:
-// 128 x 64; at least cus / 8: 64 x 64; else 32 x 64) and the batch split into runs of four
-// 64-row steps - more splits while the launch has fewer than cus / 2 workgroups, at most
-// kMaxSplits, at least one step each.  Measured at the C3 layers, B = 2048
-// (profiles/train16_wgrad_plan_sweep.json): 8 splits win at every layer, 128 x 64 at
-// 1024 x 1024 and 512 x 1024, 64 x 64 at 1024 x 479 and 256 x 512, 32 x 64 at 512 x 13
-// and 128 x 256.
-WgradPlan plan_wgrad(int64_t R, int64_t I, int64_t J, int cus, int64_t forced_tile,
-                     int64_t forced_split) {
-  const int64_t nk = ceil_div(R, kBK);
-  WgradPlan w{{int(forced_tile / 1000), int(forced_tile % 1000)}, 0, 0};
-  bool whole = false;
-  if (forced_tile == 0) {
-    const int64_t t64 = tiles_of(kTiles[2], I, J);
-    whole = tiles_of(kTiles[0], I, J) >= 2 * int64_t(cus);
-    w.tile = whole ? kTiles[0] : t64 > cus / 2 ? kTiles[1] : t64 >= cus / 8 ? kTiles[2] : kTiles[3];
-  }
-  const int64_t tiles = tiles_of(w.tile, I, J);
-  int64_t s = forced_split;
-  if (s == 0 && !whole) {
-    const int64_t fill = ceil_div(int64_t(cus) / 2, tiles > 0 ? tiles : 1);
-    s = ceil_div(nk, 4) > fill ? ceil_div(nk, 4) : fill;
-  }
-  s = s < kMaxSplits ? s : kMaxSplits;
-  s = s < nk ? s : nk;
-  s = s > 1 ? s : 1;
-  w.steps = nk > 0 ? ceil_div(nk, s) : 0;
-  w.splits = nk > 0 ? int(ceil_div(nk, w.steps)) : 1;  // every split has at least one step
-  return w;
-}
-
-bool aligned16(const void* a, int64_t lda, const void* b, int64_t ldb) {
-  return reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0 &&
-         lda % 4 == 0 && ldb % 4 == 0;
-}
 
 }  // namespace
 }  // namespace dlrm
@@ -351,19 +131,6 @@ extern "C" int dlrm_linear16_dgrad(int32_t type, int64_t M, int64_t N, int64_t K
   DLRM_LAUNCH_CHECK("dlrm_linear16_dgrad");
   return DLRM_OK;
 }
-
-namespace dlrm {
-namespace {
-// the plan of a wgrad call under the calling thread's tuning; false: a forced value is bad
-bool wgrad_plan_checked(int64_t M, int64_t N, int64_t K, WgradPlan* w) {
-  const int64_t ft = tuning(DLRM_TUNE_LINEAR16_WGRAD_TILE);
-  const int64_t fs = tuning(DLRM_TUNE_LINEAR16_WGRAD_SPLIT);
-  if (ft != 0 && !known_tile(Tile{int(ft / 1000), int(ft % 1000)})) return false;
-  *w = plan_wgrad(M, N, K, device_cus(), ft, fs);
-  return true;
-}
-}  // namespace
-}  // namespace dlrm
 
 extern "C" size_t dlrm_linear16_wgrad_workspace_size(int32_t type, int64_t M, int64_t N,
                                                      int64_t K) {

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 21
+ABI_VERSION = 22
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -59,6 +59,14 @@ class MlpChain16(ctypes.Structure):
                 ("W", c_void_p * MLP_MAX_LAYERS), ("ldw", c_int64 * MLP_MAX_LAYERS),
                 ("bias", c_void_p * MLP_MAX_LAYERS), ("bias_stride", c_int64 * MLP_MAX_LAYERS),
                 ("Y", c_void_p * MLP_MAX_LAYERS), ("ldy", c_int64 * MLP_MAX_LAYERS)]
+
+
+class Linear16BwdProblem(ctypes.Structure):
+    """struct dlrm_linear16_bwd_problem (include/dlrm_hip.h)."""
+    _fields_ = [("kind", c_int32), ("mode", c_int32), ("M", c_int64), ("N", c_int64),
+                ("K", c_int64), ("dY", c_void_p), ("lddy", c_int64), ("B", c_void_p),
+                ("ldb", c_int64), ("mask", c_void_p), ("ldmask", c_int64), ("out", c_void_p),
+                ("ldout", c_int64), ("lr", c_float), ("lr_dev", c_void_p)]
 
 
 # name -> (restype, argtypes); mirrors include/dlrm_hip.h exactly.
@@ -250,6 +258,9 @@ SIGNATURES = {
     # ABI v21: the 16-bit bottom-MLP chain (every layer on the bf16 / fp16 MFMA in one launch)
     "dlrm_mlp_chain16_supported": (c_int32, [P]),
     "dlrm_mlp_chain16_forward": (c_int32, [P, P]),
+    # ABI v22: the 16-bit Linear backward as one grouped launch (dgrads beside split wgrads)
+    "dlrm_linear16_bwd_group_workspace_size": (c_size_t, [c_int32, c_int32, P]),
+    "dlrm_linear16_bwd_group": (c_int32, [c_int32, c_int32, P, P, c_size_t, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

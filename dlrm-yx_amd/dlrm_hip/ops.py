@@ -1297,6 +1297,81 @@ def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     return out
 
 
+BWD16_DGRAD, BWD16_WGRAD = 0, 1  # dlrm_bwd16_kind
+LINEAR16_GROUP_MAX = 4
+
+
+def dgrad16_problem(g: torch.Tensor, W: torch.Tensor, mask: Optional[torch.Tensor],
+                    out: torch.Tensor):
+    """A problem of linear16_bwd_group: linear16_dgrad(g, W, mask, out)'s arguments.  The
+    returned struct holds pointers only: the caller keeps the tensors alive."""
+    fn = "dgrad16_problem"
+    _check_cuda(g, W, mask, out)
+    ldg, ldw, ldo = _row_major(g, "g", fn), _row_major(W, "W", fn), _row_major(out, "out", fn)
+    (M, N), K = g.shape, W.shape[1]
+    if W.shape[0] != N or tuple(out.shape) != (M, K):
+        raise ValueError(f"{fn}: g is [{M}, {N}], W is {list(W.shape)}, out {list(out.shape)}")
+    ldm = 0
+    if mask is not None:
+        ldm = _row_major(mask, "mask", fn)
+        if tuple(mask.shape) != (M, K):
+            raise ValueError(f"{fn}: mask is {list(mask.shape)}, expected [{M}, {K}]")
+    return _lib.Linear16BwdProblem(BWD16_DGRAD, 0, M, N, K, g.data_ptr(), ldg, W.data_ptr(), ldw,
+                                   None if mask is None else mask.data_ptr(), ldm,
+                                   out.data_ptr(), ldo, 0.0, None)
+
+
+def wgrad16_problem(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor, lr=None):
+    """A problem of linear16_bwd_group: linear16_wgrad(g, x, out, lr)'s arguments (``lr`` None:
+    out = acc; a float or a 1-element fp32 device tensor: the fused SGD step)."""
+    fn = "wgrad16_problem"
+    _check_cuda(g, x, out)
+    ldg, ldx, ldc = _row_major(g, "g", fn), _row_major(x, "x", fn), _row_major(out, "out", fn)
+    (M, N), K = g.shape, x.shape[1]
+    if x.shape[0] != M or tuple(out.shape) != (N, K):
+        raise ValueError(f"{fn}: g is [{M}, {N}], x is {list(x.shape)}, out {list(out.shape)}")
+    lr_dev = _lr_dev(lr, f"{fn}: lr")
+    host = 0.0 if lr is None or lr_dev is not None else float(lr)
+    return _lib.Linear16BwdProblem(BWD16_WGRAD, WGRAD16_STORE if lr is None else WGRAD16_SGD,
+                                   M, N, K, g.data_ptr(), ldg, x.data_ptr(), ldx, None, 0,
+                                   out.data_ptr(), ldc, host, lr_dev)
+
+
+def _bwd16_array(problems):
+    n = len(problems)
+    return n, (_lib.Linear16BwdProblem * max(n, 1))(*problems)
+
+
+def linear16_bwd_group_workspace_size(problems, dtype: str = "bf16") -> int:
+    """Bytes of workspace linear16_bwd_group needs for these problems under the calling
+    thread's tuning overrides (0: no wgrad of the group is split)."""
+    n, arr = _bwd16_array(problems)
+    return _lib.query("dlrm_linear16_bwd_group_workspace_size", MLP16_TYPES[dtype], n, arr)
+
+
+def linear16_bwd_group(problems, dtype: str = "bf16",
+                       workspace: Optional[torch.Tensor] = None, device=None) -> None:
+    """Up to four INDEPENDENT backward problems of the 16-bit Linear (dgrad16_problem /
+    wgrad16_problem) in one launch (dlrm_linear16_bwd_group); every output has the bits of
+    linear16_dgrad / linear16_wgrad under the same tuning.  Split wgrads are folded inside the
+    launch.  No problem may write what another reads or writes - nothing checks it.
+    ``workspace``: a contiguous tensor of at least linear16_bwd_group_workspace_size bytes that
+    the caller allocated ZEROED (torch.zeros); calls in stream order may share it.  The launch
+    goes to the current stream of ``device`` (default: the workspace's, else the current
+    device).  Enqueues only; allocates nothing."""
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"linear16_bwd_group: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    n, arr = _bwd16_array(problems)
+    if workspace is not None:
+        _check_cuda(workspace)
+        if not workspace.is_contiguous():
+            raise ValueError("linear16_bwd_group: workspace must be contiguous")
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    dev = device if device is not None or workspace is None else workspace.device
+    _lib.call("dlrm_linear16_bwd_group", MLP16_TYPES[dtype], n, arr, _p(workspace), ws_bytes,
+              _stream(dev))
+
+
 def eval_update(prob: torch.Tensor, target: torch.Tensor, state) -> None:
     """Append n existing probabilities and their labels to an evaluation state's log and add
     their confusion counts (dlrm_eval_update); enqueues only, capturable."""

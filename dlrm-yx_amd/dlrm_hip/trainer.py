@@ -443,6 +443,12 @@ class DLRMTrainer:
         # layers) keeps the per-layer launches.  Off by default
         self.fuse_bottom16 = False
         self.bottom16_fused = False  # set by the last build (training step or predict)
+        # the bf16 training step's MLP backward as grouped launches (dlrm_linear16_bwd_group,
+        # DESIGN.md §25): the dgrad of layer l beside the wgrad of layer l + 1, split wgrads
+        # folded inside the launch - the same bits as the three launches per layer.  Off by
+        # default
+        self.group_bwd16 = False
+        self.bwd16_grouped = False  # set by the last build of a training step
         # device TBE error bits (ops.TBE_ERR_*): out-of-range indices are skipped by the
         # kernels and flagged here; check_errors() reads it (the step never syncs)
         self.tbe_error_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -1366,22 +1372,65 @@ class DLRMTrainer:
                                        lr=lr if fused_opt else None, dtype=precision,
                                        workspace=self._ws_wgrad16(bufs, Bl, L.N, L.K + 1))
 
+            # group_bwd16: grouped launches instead (ops.linear16_bwd_group).  The wgrad of
+            # layer l + 1 rides beside the dgrad of layer l: its dY and input are complete,
+            # its update writes W[l+1], which the dgrad of the launch before has finished
+            # reading, and the launch's dgrad reads W[l].  A layer's own dgrad and SGD wgrad
+            # never share a launch (a race on W[l]).  With the wgrad one launch late the
+            # gradient must outlive two dgrads, so both MLPs rotate it over three buffers.
+            def dprob(L, g, inp, out):
+                return ops.dgrad16_problem(g[:, :L.N], L.W[:, :L.K],
+                                           None if inp is None else inp[:, :L.K], out[:, :L.K])
+
+            def wprob(L, g, inp):
+                C = L.W if fused_opt else L.gW
+                return ops.wgrad16_problem(g[:, :L.N], inp[:, :L.K + 1], C[:, :L.K + 1],
+                                           lr if fused_opt else None)
+
+            def group16(probs):
+                with prof("gemm"):
+                    ops.linear16_bwd_group(probs, dtype=precision, device=self.dev,
+                                           workspace=self._ws_group16(bufs, probs))
+
+            grouped = train and bool(self.group_bwd16)
+            if train:
+                self.bwd16_grouped = grouped
+
             def top_bwd(g):
                 G, gi = bufs["g"], 0
+                pending = []
                 for li in range(len(self.top) - 2, -1, -1):
                     L = self.top[li]
                     inp = bufs["top_act"][li - 1] if li > 0 else bufs["R"]
                     gn = (gi + 1) % 3
-                    dgrad16(L, g, inp if li > 0 else None, G[gn])
-                    wgrad16(L, g, inp)
+                    if grouped:
+                        group16([dprob(L, g, inp if li > 0 else None, G[gn])] + pending)
+                        pending = [wprob(L, g, inp)]
+                    else:
+                        dgrad16(L, g, inp if li > 0 else None, G[gn])
+                        wgrad16(L, g, inp)
                     g, gi = G[gn], gn
+                if pending:
+                    group16(pending)
                 return g
 
             def bottom_bwd():
                 g = bufs["gx"]  # dLoss/d(pre-ReLU bottom output), from the interaction backward
+                pending = []
                 for li in range(self.n_bot - 1, -1, -1):
                     L = self.bot[li]
                     inp = bufs["bot_act"][li - 1] if li > 0 else batch.X
+                    if grouped:
+                        # the last launch holds the two lowest wgrads (different W, nothing
+                        # written that the other reads)
+                        w = wprob(L, g, inp)
+                        if li > 0:
+                            out = bufs["gb"][li % 3]
+                            group16([dprob(L, g, inp, out)] + pending)
+                            pending, g = [w], out
+                        else:
+                            group16(pending + [w])
+                        continue
                     if li > 0:
                         dgrad16(L, g, inp, bufs["gb"][li % 2])
                     wgrad16(L, g, inp)
@@ -1617,6 +1666,19 @@ class DLRMTrainer:
                 raise RuntimeError("capture() needs one eager step of this batch size first "
                                    "(the wgrad workspace)")
             ws = bufs["wgrad16_ws"] = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        return ws
+
+    def _ws_group16(self, bufs, probs) -> Optional[torch.Tensor]:
+        """The batch size's linear16_bwd_group workspace (tickets + split records; its launches
+        run in stream order and share it), allocated ZEROED and grown on the eager steps only:
+        every launch leaves the tickets zero, a captured graph keeps the address."""
+        need = ops.linear16_bwd_group_workspace_size(probs, self.cfg.mlp_precision)
+        ws = bufs.get("group16_ws")
+        if need and (ws is None or ws.numel() < need):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capture() needs one eager step of this batch size first "
+                                   "(the grouped backward's workspace)")
+            ws = bufs["group16_ws"] = torch.zeros(need, dtype=torch.uint8, device=self.dev)
         return ws
 
     @staticmethod

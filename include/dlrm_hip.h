@@ -152,8 +152,12 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 21: the 16-bit bottom-MLP chain: dlrm_mlp_chain16 / dlrm_mlp_chain16_supported /
  *    dlrm_mlp_chain16_forward (up to four Linear+ReLU layers on the bf16 / fp16 MFMA in one
  *    launch, the activations rounded once into LDS; the bits of dlrm_linear16_forward applied
- *    layer by layer). */
-#define DLRM_ABI_VERSION 21/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    layer by layer).
+ * 22: the 16-bit Linear backward as a grouped launch: dlrm_linear16_bwd_problem /
+ *    dlrm_linear16_bwd_group (+ _workspace_size): up to four independent dgrads / wgrads of
+ *    ABI v13 in one launch, split wgrads folded inside it by the last-arriving workgroup of a
+ *    tile (no reduce launch); the bits of dlrm_linear16_dgrad / dlrm_linear16_wgrad. */
+#define DLRM_ABI_VERSION 22/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -1285,6 +1289,56 @@ int dlrm_linear16_wgrad_dev(int32_t type, int64_t M, int64_t N, int64_t K, const
                             int64_t lddy, const float* X, int64_t ldx, int32_t mode,
                             const float* lr_dev, float* C, int64_t ldc, void* workspace,
                             size_t workspace_bytes, dlrm_stream_t stream);
+
+
+/* ------------------------------------- 16-bit training Linear, grouped launch -- */
+/*
+ * ABI v22.  One launch runs n (1 .. 4) backward problems of the 16-bit Linear, each with the
+ * semantics, the checks, the status codes and the plan (tuning overrides included) of the
+ * stand-alone call on the same arguments:
+ *   DLRM_BWD16_DGRAD: dlrm_linear16_dgrad - B is W [N][K], out is dX [M][K], mask as there
+ *                     (NULL: none); mode / lr / lr_dev are ignored.
+ *   DLRM_BWD16_WGRAD: dlrm_linear16_wgrad - B is X [M][K], out is C [N][K], mode is a
+ *                     dlrm_wgrad16_mode; lr_dev == NULL: the host `lr`, else the device fp32
+ *                     replaces it (ABI v14; only with DLRM_WGRAD16_SGD).  The SGD step is
+ *                     C = fma(-lr, acc, C), one rounding, as dlrm_linear16_wgrad computes it.
+ * Every output equals, bit for bit, what the stand-alone call writes under the same tuning.
+ * A wgrad whose plan splits the reduction is completed INSIDE the launch: the last-arriving
+ * workgroup of a tile sums the partial tiles in split order and applies STORE / SGD; there
+ * is no second launch, no floating-point atomic, and no workgroup waits on another.
+ *
+ * THE PROBLEMS OF ONE CALL MUST BE INDEPENDENT: they run concurrently, so no problem may
+ * write (out) what another reads or writes (dY, B, mask, out).  In particular a layer's
+ * dgrad (reads W) and the same layer's SGD wgrad (updates W) must not share a call.  The
+ * entry point cannot verify this.
+ *
+ * workspace: dlrm_linear16_bwd_group_workspace_size bytes (0: no problem is split; a larger
+ * workspace is fine), 16-byte aligned, ZEROED ONCE by the caller before its first use; every
+ * call leaves its head (the tiles' tickets) zero again, so calls in stream order - and
+ * replays of a captured graph - may share it.  At most 4096 split tiles per call
+ * (DLRM_ERR_UNSUPPORTED beyond).  Nothing is enqueued when a status other than DLRM_OK is
+ * returned.
+ */
+enum dlrm_bwd16_kind { DLRM_BWD16_DGRAD = 0, DLRM_BWD16_WGRAD = 1 };
+typedef struct dlrm_linear16_bwd_problem {
+  int32_t kind;      /* dlrm_bwd16_kind */
+  int32_t mode;      /* wgrad: dlrm_wgrad16_mode */
+  int64_t M, N, K;
+  const float* dY;   /* [M][N] */
+  int64_t lddy;
+  const float* B;    /* dgrad: W [N][K]; wgrad: X [M][K] */
+  int64_t ldb;
+  const float* mask; /* dgrad: [M][K] or NULL */
+  int64_t ldmask;
+  float* out;        /* dgrad: dX [M][K]; wgrad: C [N][K] */
+  int64_t ldout;
+  float lr;          /* wgrad, DLRM_WGRAD16_SGD */
+  const float* lr_dev; /* NULL: the host lr */
+} dlrm_linear16_bwd_problem;
+size_t dlrm_linear16_bwd_group_workspace_size(int32_t type, int32_t n,
+                                              const dlrm_linear16_bwd_problem* problems);
+int dlrm_linear16_bwd_group(int32_t type, int32_t n, const dlrm_linear16_bwd_problem* problems,
+                            void* workspace, size_t workspace_bytes, dlrm_stream_t stream);
 
 #ifdef __cplusplus
 }

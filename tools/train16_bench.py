@@ -15,7 +15,7 @@ touched):
 
 Writes one JSON document to --out (default profiles/train16_bench.json) and prints it.
 python tools/train16_bench.py [--config terabyte] [--steps 200] [--rounds 3] [--skip-step]
-[--skip-layers]"""
+[--skip-layers] [--group16]"""
 import argparse
 import json
 import os
@@ -63,14 +63,16 @@ def _trainer(config, dev, precision):
     return c, DLRMTrainer(cfg, device=dev, seed=1)
 
 
-def step_timing(config, steps, warmup, rounds, dev):
+def step_timing(config, steps, warmup, rounds, dev, group16=False):
     import bench
-    modes = ("fp32", "bf16")
+    # --group16: a third trainer, the bf16 step with DLRMTrainer.group_bwd16 on
+    modes = ("fp32", "bf16") + (("bf16_group",) if group16 else ())
     runs = {}
     nb = 10
     pool = torch.cuda.graph_pool_handle()
     for mode in modes:
-        c, tr = _trainer(config, dev, mode)
+        c, tr = _trainer(config, dev, mode.split("_")[0])
+        tr.group_bwd16 = mode == "bf16_group"
         batches = [tr.synthetic_batch(c["B"], c["L"], seed=100 + i) for i in range(nb)]
         for b in batches[:3]:
             tr.step(b)
@@ -99,6 +101,12 @@ def step_timing(config, steps, warmup, rounds, dev):
     res = dict(config=config, batch=c["B"], ms_per_step={m: _stats(w) for m, w in windows.items()})
     res["bf16_over_fp32"] = round(res["ms_per_step"]["bf16"]["median"] /
                                   res["ms_per_step"]["fp32"]["median"], 4)
+    if group16:
+        assert runs["bf16_group"][0].bwd16_grouped and not runs["bf16"][0].bwd16_grouped
+        a, b = res["ms_per_step"]["bf16"], res["ms_per_step"]["bf16_group"]
+        res["group_over_bf16"] = round(b["median"] / a["median"], 4)
+        # a difference counts only beyond the spread between a mode's own windows
+        res["group_differs"] = bool(abs(a["median"] - b["median"]) > max(a["spread"], b["spread"]))
     return res
 
 
@@ -179,6 +187,8 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--skip-layers", action="store_true")
+    ap.add_argument("--group16", action="store_true",
+                    help="time the bf16 step with group_bwd16 on beside the other two")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train16_bench.json"))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -188,7 +198,8 @@ def main():
         res["layers"] = layer_timing(args.config, args.reps, args.rounds, dev)
         torch.cuda.empty_cache()
     if not args.skip_step:
-        res["step"] = step_timing(args.config, args.steps, args.warmup, args.rounds, dev)
+        res["step"] = step_timing(args.config, args.steps, args.warmup, args.rounds, dev,
+                                  args.group16)
     text = json.dumps(res, indent=1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
