@@ -21,9 +21,9 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace dlrm
 
-// ABI v17 - v22: the version is only reported by a library that links the entry points it names
+// ABI v17 - v23: the version is only reported by a library that links the entry points it names
 // (taking their addresses with the header's types fails the build if one is missing).
-static_assert(DLRM_ABI_VERSION >= 22, "abi.cpp checks the v17 - v22 entry points");
+static_assert(DLRM_ABI_VERSION >= 23, "abi.cpp checks the v17 - v23 entry points");
 namespace {
 [[maybe_unused]] int (*const kLinear8Pack)(int64_t, int64_t, const float*, int64_t, int8_t*,
                                            int64_t, float*, void*, size_t,
@@ -59,6 +59,13 @@ namespace {
     &dlrm_linear16_bwd_group_workspace_size;
 [[maybe_unused]] int (*const kBwd16Group)(int32_t, int32_t, const dlrm_linear16_bwd_problem*, void*,
                                           size_t, dlrm_stream_t) = &dlrm_linear16_bwd_group;
+[[maybe_unused]] int (*const kTbeAdagradF16)(void*, float*, int64_t, const int64_t*, int32_t,
+                                             int32_t, const void*, int32_t, const void*, int32_t,
+                                             int64_t, int64_t, const float*, const float*,
+                                             int64_t, float, const float*, float,
+                                             const uint64_t*, int64_t, void*, size_t, int32_t*,
+                                             int32_t,
+                                             dlrm_stream_t) = &dlrm_tbe_backward_rowwise_adagrad_f16;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

@@ -1051,7 +1051,7 @@ struct UpdateGeom {
 };
 
 int plan_update(const BwdCall& c, UpdateGeom& u) {
-  const bool f16_rows = c.mode == MODE_SGD_F16 || c.mode == MODE_SGD_F16_SR;
+  const bool f16_rows = mode_f16_rows(c.mode);  // uint2 of four halves: 8-byte rows
   // (element-wise Adagrad: the state rows are read and written like the weight rows)
   u.vec4 = (c.D % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.W) & (f16_rows ? 7 : 15)) == 0) &&
            (c.mode != MODE_ADAGRAD_ELEM || (reinterpret_cast<uintptr_t>(c.mom) & 15) == 0) &&
@@ -1075,6 +1075,8 @@ void for_mode(int mode, F&& f) {
     case MODE_SGD_F16: return f(int_tag<MODE_SGD_F16>{});
     case MODE_SGD_F16_SR: return f(int_tag<MODE_SGD_F16_SR>{});
     case MODE_ADAGRAD_ELEM: return f(int_tag<MODE_ADAGRAD_ELEM>{});
+    case MODE_ADAGRAD_F16: return f(int_tag<MODE_ADAGRAD_F16>{});
+    case MODE_ADAGRAD_F16_SR: return f(int_tag<MODE_ADAGRAD_F16_SR>{});
     default: return f(int_tag<MODE_DENSE>{});
   }
 }
@@ -1314,6 +1316,33 @@ extern "C" int dlrm_tbe_backward_rowwise_adagrad_dev(
   c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
   c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
   c.gout = grad_out, c.gbs = grad_batch_stride, c.lr_dev = lr_dev, c.eps = eps;
+  c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
+  c.err = error_flag, c.presorted = presorted, c.stream = stream;
+  return bwd_dispatch(c);
+}
+
+// ABI v23: row-wise Adagrad on fp16 rows.  The momentum and the updated row are
+// dlrm_tbe_backward_rowwise_adagrad's on the widened halves; sr_state selects the store
+// (NULL: nearest even; else the stochastic store of dlrm_tbe_backward_sgd_f16_sr).
+extern "C" int dlrm_tbe_backward_rowwise_adagrad_f16(
+    void* weights, float* momentum, int64_t D, const int64_t* row_base, int32_t T, int32_t B,
+    const void* indices, int32_t index_bits, const void* offsets, int32_t offset_bits,
+    int64_t num_lookups, int64_t total_rows, const float* per_sample_weights,
+    const float* grad_out, int64_t grad_batch_stride, float lr, const float* lr_dev, float eps,
+    const uint64_t* sr_state, int64_t max_lookups_per_table, void* workspace,
+    size_t workspace_bytes, int32_t* error_flag, int32_t presorted, dlrm_stream_t stream) {
+  BwdCall c{};
+  c.name = "dlrm_tbe_backward_rowwise_adagrad_f16";
+  c.mode = sr_state ? MODE_ADAGRAD_F16_SR : MODE_ADAGRAD_F16;
+  DLRM_ARG(momentum, "%s: null momentum", c.name);
+  DLRM_ARG((reinterpret_cast<uintptr_t>(sr_state) & 7) == 0,
+           "%s: sr_state must be NULL or an 8-byte aligned device pointer", c.name);
+  c.W = static_cast<float*>(weights), c.mom = momentum;
+  c.D = D, c.row_base = row_base, c.T = T, c.B = B;
+  c.idx = indices, c.index_bits = index_bits, c.off = offsets, c.offset_bits = offset_bits;
+  c.N = num_lookups, c.total_rows = total_rows, c.psw = per_sample_weights;
+  c.gout = grad_out, c.gbs = grad_batch_stride;
+  c.lr = lr_dev ? 0.f : lr, c.lr_dev = lr_dev, c.eps = eps, c.sr_state = sr_state;
   c.max_seg = max_lookups_per_table, c.ws = workspace, c.ws_bytes = workspace_bytes;
   c.err = error_flag, c.presorted = presorted, c.stream = stream;
   return bwd_dispatch(c);

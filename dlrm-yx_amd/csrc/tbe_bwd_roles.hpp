@@ -22,6 +22,10 @@ constexpr int64_t kLongChN = 1 << 18;
 // as fp16, updated in fp32 and stored back rounded to nearest even.
 // MODE_SGD_F16_SR: the same update in every respect but the store, which rounds
 // stochastically (sr16_bits) with the element's draw of the call's (seed, step) stream.
+// MODE_ADAGRAD_F16 / MODE_ADAGRAD_F16_SR: row-wise Adagrad on fp16 weights (the fbgemm TBE's
+// FP16 tables under EXACT_ROWWISE_ADAGRAD): the row is read as fp16 and widened, the momentum
+// (fp32, one per row) and the updated row are MODE_ADAGRAD's operation for operation, and the
+// row is stored back rounded to nearest even, or stochastically as MODE_SGD_F16_SR stores.
 // MODE_ADAGRAD_ELEM: element-wise Adagrad (torch.optim.Adagrad): `mom` is the state S,
 // [total_rows, D] fp32 in the layout of W, one accumulator per weight.  The arithmetic is
 // adagrad_kernel's (misc.hip), operation for operation, so a sparse update equals the dense
@@ -32,12 +36,25 @@ enum {
   MODE_DENSE = 2,
   MODE_SGD_F16 = 3,
   MODE_SGD_F16_SR = 4,
-  MODE_ADAGRAD_ELEM = 5
+  MODE_ADAGRAD_ELEM = 5,
+  MODE_ADAGRAD_F16 = 6,
+  MODE_ADAGRAD_F16_SR = 7
 };
+inline constexpr bool mode_f16_rows(int mode) {
+  return mode == MODE_SGD_F16 || mode == MODE_SGD_F16_SR || mode == MODE_ADAGRAD_F16 ||
+         mode == MODE_ADAGRAD_F16_SR;
+}
 template <int MODE>
-constexpr bool kF16Rows = MODE == MODE_SGD_F16 || MODE == MODE_SGD_F16_SR;
+constexpr bool kF16Rows = mode_f16_rows(MODE);
+// the store draws from the call's stochastic-rounding stream
 template <int MODE>
-constexpr bool kSgdMode = MODE == MODE_SGD || kF16Rows<MODE>;
+constexpr bool kSrStore = MODE == MODE_SGD_F16_SR || MODE == MODE_ADAGRAD_F16_SR;
+template <int MODE>
+constexpr bool kSgdMode = MODE == MODE_SGD || MODE == MODE_SGD_F16 || MODE == MODE_SGD_F16_SR;
+// row-wise Adagrad: one fp32 momentum per row, on fp32 or fp16 rows
+template <int MODE>
+constexpr bool kRowwiseMode =
+    MODE == MODE_ADAGRAD || MODE == MODE_ADAGRAD_F16 || MODE == MODE_ADAGRAD_F16_SR;
 
 // Weight-row element access by mode: fp32 rows, or fp16 rows (W then points at halves).
 template <int MODE, int VW>
@@ -59,11 +76,22 @@ __device__ __forceinline__ typename VecT<VW>::T wload(const float* __restrict__ 
   }
 }
 
-// sr: the call's stochastic-rounding key (sr_load_key; MODE_SGD_F16_SR only, else unused)
+// The update's fp32 value as a value of its own.  Left to the compiler, fmaf(-lr, u, (float)h)
+// followed by the conversion to fp16 may become ONE v_fma_mixlo_f16: the exact sum rounded
+// straight to fp16, which differs from half_rne(v) wherever the fp32 rounding of v lands on an
+// fp16 tie - and whether it does depends on the lane shape and the build's flags.  Every fp16
+// store is specified on v (the fp32-row kernel's value), so v is pinned in a register between
+// its two roundings.
+__device__ __forceinline__ float pinned_f32(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// sr: the call's stochastic-rounding key (sr_load_key; the kSrStore modes only, else unused)
 template <int MODE, int VW>
 __device__ __forceinline__ void wstore(float* __restrict__ W, int64_t row, int64_t D, int chunk,
                                        const typename VecT<VW>::T& v, uint64_t sr) {
-  if constexpr (MODE == MODE_SGD_F16_SR) {
+  if constexpr (kSrStore<MODE>) {
     _Float16* h = reinterpret_cast<_Float16*>(W) + row * D + (int64_t)chunk * VW;
     const uint64_t chunks4 = (uint64_t)((D + 3) >> 2);
     if constexpr (VW == 4) {
@@ -79,16 +107,17 @@ __device__ __forceinline__ void wstore(float* __restrict__ W, int64_t row, int64
       const uint32_t r = (uint32_t)(x >> (16 * (chunk & 3))) & 0xffffu;
       h[0] = __builtin_bit_cast(_Float16, (unsigned short)sr16_bits(v, r));
     }
-  } else if constexpr (MODE == MODE_SGD_F16) {
+  } else if constexpr (kF16Rows<MODE>) {
     _Float16* h = reinterpret_cast<_Float16*>(W) + row * D + (int64_t)chunk * VW;
+    auto half_of = [](float f) { return (_Float16)pinned_f32(f); };
     if constexpr (VW == 4) {
-      auto bits = [](float f) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f); };
+      auto bits = [&](float f) { return (uint32_t)__builtin_bit_cast(unsigned short, half_of(f)); };
       uint2 u;
       u.x = bits(v.x) | (bits(v.y) << 16);
       u.y = bits(v.z) | (bits(v.w) << 16);
       *reinterpret_cast<uint2*>(h) = u;
     } else {
-      h[0] = (_Float16)v;
+      h[0] = half_of(v);
     }
   } else {
     reinterpret_cast<typename VecT<VW>::T*>(W + row * D)[chunk] = v;
@@ -149,7 +178,8 @@ __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __res
         wrow[chunk] = w;
       }
     }
-  } else {  // RWSAdagrad: momentum += mean(g^2); w -= lr * g / (sqrt(momentum) + eps)
+  } else {  // RWSAdagrad: momentum += mean(g^2); w -= lr * g / (sqrt(momentum) + eps);
+            // fp32 rows, or fp16 rows widened on load and rounded on store
     float sq = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXV; ++c)
@@ -163,7 +193,7 @@ __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __res
     for (int c = 0; c < MAXV; ++c) {
       const int chunk = gl + c * LPB;
       if (chunk < nchunks) {
-        V w = wrow[chunk];
+        V w = wload<MODE, VW>(W, row, D, chunk);
         V u = g[c];
         if constexpr (VW == 4) {
           u.x /= denom;
@@ -174,7 +204,7 @@ __device__ __forceinline__ void finalize_row(float* __restrict__ W, float* __res
           u /= denom;
         }
         vfma(w, -lr, u);
-        wrow[chunk] = w;
+        wstore<MODE, VW>(W, row, D, chunk, w, sr);
       }
     }
   }
@@ -251,7 +281,7 @@ __device__ __forceinline__ void finalize_row_pf(float* __restrict__ W, float* __
           u /= denom;
         }
         vfma(x, -lr, u);
-        wrow[chunk] = x;
+        wstore<MODE, VW>(W, row, D, chunk, x, sr);
       }
     }
   }
@@ -411,7 +441,7 @@ __device__ __forceinline__ void tbe_bwd_block_body(
               else
                 vzero(wv[u][c]);
             }
-            mv[u] = (MODE == MODE_ADAGRAD && lead) ? mom[ku[u]] : 0.f;
+            mv[u] = (kRowwiseMode<MODE> && lead) ? mom[ku[u]] : 0.f;
           }
         }
 #pragma unroll
@@ -548,7 +578,7 @@ __global__ __launch_bounds__(256) void tbe_bwd_block_kernel(
     KeyT sentinel, float* __restrict__ partial, int ch, const float* __restrict__ lr_dev,
     const uint64_t* __restrict__ sr_state) {
   uint64_t sr = 0;
-  if constexpr (MODE == MODE_SGD_F16_SR) sr = sr_load_key(sr_state);
+  if constexpr (kSrStore<MODE>) sr = sr_load_key(sr_state);
   tbe_bwd_block_body<LPB, VW, MAXV, KeyT, MODE, SB>(W, mom, D, B, keys, pos, bag_of, psw, gout,
                                                     gbs, N, dlrm_resolve_lr(lr_dev, lr), eps,
                                                     sentinel, partial, ch, blockIdx.x, gridDim.x,
@@ -561,7 +591,7 @@ __global__ __launch_bounds__(256) void tbe_bwd_combine_kernel(
     int64_t N, float lr, float eps, KeyT sentinel, const float* __restrict__ partial, int ch,
     const float* __restrict__ lr_dev, const uint64_t* __restrict__ sr_state) {
   uint64_t sr = 0;
-  if constexpr (MODE == MODE_SGD_F16_SR) sr = sr_load_key(sr_state);
+  if constexpr (kSrStore<MODE>) sr = sr_load_key(sr_state);
   tbe_bwd_combine_body<LPB, VW, MAXV, KeyT, MODE>(W, mom, D, keys, N,
                                                   dlrm_resolve_lr(lr_dev, lr), eps, sentinel,
                                                   partial, ch, blockIdx.x, gridDim.x, sr);

@@ -13,7 +13,7 @@ from ctypes import c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DLRM_ABI_VERSION of include/dlrm_hip.h that these signatures mirror; load() refuses a
 # library built from any other header (tests/test_cpu_host.py checks header == this).
-ABI_VERSION = 22
+ABI_VERSION = 23
 LIB_PATH = os.environ.get("DLRM_HIP_LIB", os.path.join(_HERE, "libdlrm_hip.so"))
 
 
@@ -261,6 +261,12 @@ SIGNATURES = {
     # ABI v22: the 16-bit Linear backward as one grouped launch (dgrads beside split wgrads)
     "dlrm_linear16_bwd_group_workspace_size": (c_size_t, [c_int32, c_int32, P]),
     "dlrm_linear16_bwd_group": (c_int32, [c_int32, c_int32, P, P, c_size_t, P]),
+    # ABI v23: row-wise Adagrad on fp16 rows (host rate + NULL, or a device rate; the sr state
+    # or NULL for the nearest-even store)
+    "dlrm_tbe_backward_rowwise_adagrad_f16": (c_int32, [P, P, c_int64, P, c_int32, c_int32, P,
+                                                        c_int32, P, c_int32, c_int64, c_int64, P,
+                                                        P, c_int64, c_float, P, c_float, P,
+                                                        c_int64, P, c_size_t, P, c_int32, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

@@ -199,14 +199,23 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
     does): the store is rounded stochastically instead (dlrm_tbe_backward_sgd_f16_sr) from
     the counter-based stream of (``seed``, step, row, column) - the module owns the device
     state (the ``sr_state`` buffer, in its state_dict) and ticks it after each fused update.
+    ``optimizer="rowwise_adagrad"`` (or Optimizer.EXACT_ROWWISE_ADAGRAD; fbgemm's
+    OptimType.EXACT_ROWWISE_ADAGRAD): the fused update is dlrm_tbe_backward_rowwise_adagrad_f16
+    with ``eps`` - fp32 arithmetic and an fp32 ``momentum`` buffer [rows] in the state_dict,
+    fp16 rows, either store.  The default stays exact SGD.
     fbgemm_gpu itself is not in the reference tree, so its init bound, its LFU cache and
     its random stream are not reproduced (parity unpinned against it); tables are drawn
     U(+-sqrt(1/n)) like the other DLRM paths."""
 
     def __init__(self, embedding_specs, learning_rate: float = 0.01, eps: float = 1.0e-8,
                  tables=None, seed: int = 0, device=None, stochastic_rounding: bool = False,
-                 **unused):
+                 optimizer="sgd", **unused):
         super().__init__()
+        if optimizer in (Optimizer.SGD, Optimizer.EXACT_ROWWISE_ADAGRAD):
+            optimizer = "sgd" if optimizer == Optimizer.SGD else "rowwise_adagrad"
+        if optimizer not in ("sgd", "rowwise_adagrad"):
+            raise ValueError(f"optimizer {optimizer!r}: 'sgd' or 'rowwise_adagrad'")
+        self.optimizer = optimizer
         Es = [int(e) for e, *_ in embedding_specs]
         Ds = {int(d) for _, d, *_ in embedding_specs}
         if len(Ds) != 1:
@@ -233,6 +242,8 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
         self.weights = Parameter(w.half(), requires_grad=True)
         self.register_buffer("table_offsets", torch.tensor([0] + [b for _, b in self.row_ranges],
                                                            dtype=torch.int64))
+        if optimizer == "rowwise_adagrad":
+            self.register_buffer("momentum", torch.zeros(total))
         self.stochastic_rounding = bool(stochastic_rounding)
         if self.stochastic_rounding:  # dlrm_sr_state: the uint64 bits of (seed, step = 0)
             self.register_buffer("sr_state", torch.tensor([ops._as_i64(seed), 0],
@@ -250,14 +261,16 @@ class SplitTableBatchedEmbeddingBags(nn.Module):
         return self.table_offsets
 
     def fused_update(self, indices, offsets, grad, psw, B):
+        kw = dict(lr=self.learning_rate, per_sample_weights=psw)
+        if self.optimizer == "rowwise_adagrad":
+            kw.update(eps=self.eps, momentum=self.momentum)
         if self.stochastic_rounding:
-            ops.tbe_backward("sgd", self.weights.data, self.table_offsets, self.T, B, indices,
-                             offsets, grad, lr=self.learning_rate, per_sample_weights=psw,
-                             sr_state=self.sr_state)
+            ops.tbe_backward(self.optimizer, self.weights.data, self.table_offsets, self.T, B,
+                             indices, offsets, grad, sr_state=self.sr_state, **kw)
             ops.sr_tick(self.sr_state)
             return
-        ops.tbe_backward("sgd", self.weights.data, self.table_offsets, self.T, B, indices,
-                         offsets, grad, lr=self.learning_rate, per_sample_weights=psw)
+        ops.tbe_backward(self.optimizer, self.weights.data, self.table_offsets, self.T, B,
+                         indices, offsets, grad, **kw)
 
     def split_embedding_weights(self) -> List[torch.Tensor]:
         return [self.weights.data[a:b] for a, b in self.row_ranges]

@@ -397,6 +397,8 @@ _TBE_BWD = {
     "dense": ("dlrm_tbe_backward_dense", False, None, False),
 }
 _TBE_BWD_SR = ("dlrm_tbe_backward_sgd_f16_sr", False, "both", False)  # then the sr state
+# fp16 rows under row-wise Adagrad: one entry, eps and then the sr state or NULL after the rate
+_TBE_BWD_RWS_F16 = ("dlrm_tbe_backward_rowwise_adagrad_f16", True, "both", True)
 
 
 def tbe_backward_sort(weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
@@ -425,7 +427,8 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
                  sr_state: Optional[torch.Tensor] = None) -> None:
     """mode: 'sgd' (fused exact SGD; fp32 or fp16 weights; 'sgd_f16' names the fp16 case and
     refuses fp32 weights), 'rowwise_adagrad' (fused
-    RWSAdagrad), 'adagrad' (fused element-wise torch.optim.Adagrad on fp32 weights;
+    RWSAdagrad; fp32 weights, or fp16 weights with the fp32 ``momentum``:
+    dlrm_tbe_backward_rowwise_adagrad_f16), 'adagrad' (fused element-wise torch.optim.Adagrad on fp32 weights;
     ``momentum`` is its "sum" state, contiguous fp32 of the weights' shape, and the result
     equals 'dense' into a zero buffer followed by adagrad_update over the whole table, bit
     for bit) or 'dense' (weights is a gradient buffer to accumulate into).  max_lookups_per_table:
@@ -438,18 +441,23 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     kernels run.
     ``sr_state`` (fp16 weights only; ops.sr_state): the updated row is stored rounded
     stochastically with the state's (seed, step) stream instead of to nearest even
-    (dlrm_tbe_backward_sgd_f16_sr); the state is read when the kernels run, never written."""
+    (dlrm_tbe_backward_sgd_f16_sr, or the row-wise Adagrad entry); the state is read when the
+    kernels run, never written."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     lr_dev = _lr_dev(lr, "tbe_backward: lr")
-    if sr_state is not None and not (mode in ("sgd", "sgd_f16")
+    rws_f16 = mode == "rowwise_adagrad" and weights.dtype == torch.float16
+    if sr_state is not None and not (mode in ("sgd", "sgd_f16", "rowwise_adagrad")
                                      and weights.dtype == torch.float16):
-        raise ValueError("tbe_backward: sr_state goes with 'sgd' / 'sgd_f16' on fp16 weights")
+        raise ValueError("tbe_backward: sr_state goes with 'sgd' / 'sgd_f16' / "
+                         "'rowwise_adagrad' on fp16 weights")
     head, tail = _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights,
                                workspace, max_lookups_per_table, error_flag,
                                (grad_out, grad_batch_stride))
     if mode == "sgd_f16" and weights.dtype != torch.float16:
         raise ValueError("tbe_backward: mode 'sgd_f16' takes fp16 weights")
-    if sr_state is not None:
+    if rws_f16:
+        entry = _TBE_BWD_RWS_F16
+    elif sr_state is not None:
         entry = _TBE_BWD_SR
     elif mode in ("sgd", "sgd_f16") and weights.dtype == torch.float16:
         entry = _TBE_BWD["sgd_f16"]
@@ -457,6 +465,10 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
         entry = _TBE_BWD[mode]
     else:
         raise ValueError(mode)
+    if rws_f16 and (momentum is None or momentum.dtype != torch.float32
+                    or momentum.numel() < weights.shape[0]):
+        raise ValueError("tbe_backward: 'rowwise_adagrad' on fp16 weights keeps its momentum "
+                         f"in fp32, one per row: momentum= is fp32 [{weights.shape[0]}]")
     if mode == "adagrad":
         if weights.dtype != torch.float32:
             raise ValueError("tbe_backward: mode 'adagrad' takes fp32 weights")
@@ -473,10 +485,13 @@ def tbe_backward(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: in
     elif rate_as == "split":
         rate = (lr,) if lr_dev is None else (lr_dev,)
         name += "" if lr_dev is None else "_dev"
-    if sr_state is not None:
-        rate += (_sr_ptr(sr_state, "tbe_backward"),)
+    state = () if sr_state is None else (_sr_ptr(sr_state, "tbe_backward"),)
+    if rws_f16:  # after eps; NULL selects the nearest-even store
+        state = (eps,) + (state or (None,))
+    elif with_eps:
+        state += (eps,)
     _lib.call(name, _p(weights), *((_p(momentum),) if with_state else ()), *head, *rate,
-              *((eps,) if with_eps else ()), *tail, int(presorted), _stream(weights.device))
+              *state, *tail, int(presorted), _stream(weights.device))
 
 
 def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor, T: int, B: int,
@@ -496,7 +511,8 @@ def tbe_backward_defer(mode: str, weights: torch.Tensor, row_base: torch.Tensor,
     role then carries its address: both passes read it when their launch runs)."""
     _check_cuda(weights, row_base, indices, offsets, grad_out, momentum, per_sample_weights)
     if weights.dtype != torch.float32 or mode not in ("sgd", "rowwise_adagrad"):
-        raise ValueError("tbe_backward_defer: fp32 'sgd' or 'rowwise_adagrad' only")
+        raise ValueError("tbe_backward_defer: fp32 'sgd' or 'rowwise_adagrad' only (the fp16 "
+                         "rows' updates run as launches of their own)")
     head, tail = _tbe_bwd_args(weights, row_base, T, B, indices, offsets, per_sample_weights,
                                workspace, max_lookups_per_table, error_flag,
                                (grad_out, grad_batch_stride))

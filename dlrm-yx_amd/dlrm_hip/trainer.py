@@ -23,8 +23,9 @@ optimizer update.  Layout decisions (MI355X-first):
 * Mixed precision on request (TrainerConfig.mlp_precision = "bf16"): the MLP layers below the
   head run forward, data gradient and weight gradient on the bf16 MFMA from the same fp32
   buffers (the 16-bit closures of DLRMTrainer._build); everything above stays as described.
-* fp16 tables on request (TrainerConfig.emb_precision = "fp16", one GPU, SGD): the row buffer
-  is [sum rows, D] half (C3: 13.9 GB); the gather-fused interaction and the pooled lookup
+* fp16 tables on request (TrainerConfig.emb_precision = "fp16", one GPU, SGD - or row-wise
+  Adagrad with an fp32 momentum where emb_optimizer = "rwsadagrad" asks for it, DESIGN.md
+  §26): the row buffer is [sum rows, D] half (C3: 13.9 GB); the gather-fused interaction and the pooled lookup
   widen a row as they load it, the update rounds the new row to nearest even as it stores it
   (an update below half an fp16 ulp of the weight vanishes) or, with emb_rounding =
   "stochastic", up or down at random in proportion (a device (seed, step) stream, ticked
@@ -86,6 +87,12 @@ class TrainerConfig:
     # sgd | rwsadagrad | adagrad (torch.optim.Adagrad, the reference's --optimizer adagrad:
     # one accumulator per weight, the tables' in a second [rows, D] fp32 buffer)
     optimizer: str = "sgd"
+    # the embedding tables' optimizer: None = as `optimizer`, or "sgd" | "rwsadagrad" chosen
+    # independently of the dense weights' (the usual TBE configuration: dense SGD, sparse
+    # row-wise Adagrad); `optimizer` then names the dense path alone and must be "sgd" or
+    # "rwsadagrad".  Set explicitly, "rwsadagrad" also runs on emb_precision="fp16" tables:
+    # fp32 momentum, fp16 rows
+    emb_optimizer: Optional[str] = None
     adagrad_eps: float = 1e-10
     sharder: str = "greedy"
     allocation: Optional[Sequence[int]] = None
@@ -139,6 +146,11 @@ class TrainerConfig:
                 int(self.lr_num_decay_steps))
 
     @property
+    def emb_opt(self) -> str:
+        """The tables' optimizer: emb_optimizer, or `optimizer` where it is None."""
+        return self.optimizer if self.emb_optimizer is None else self.emb_optimizer
+
+    @property
     def lr_mode(self) -> str:
         """"device": learning rates in device memory (a policy, or device_lr); else "host"."""
         return "device" if self.device_lr or any(self.lr_policy_steps) else "host"
@@ -158,24 +170,35 @@ class TrainerConfig:
         if self.emb_rounding == "stochastic" and self.emb_precision != "fp16":
             raise ValueError("emb_rounding='stochastic' rounds the fp16 tables' update: it "
                              "needs emb_precision='fp16'")
+        if self.emb_optimizer is not None:
+            if self.emb_optimizer not in ("sgd", "rwsadagrad"):
+                raise ValueError(f"emb_optimizer {self.emb_optimizer!r}: None, 'sgd' or "
+                                 "'rwsadagrad'")
+            if self.optimizer not in ("sgd", "rwsadagrad"):
+                raise ValueError(f"emb_optimizer is set: optimizer {self.optimizer!r} names the "
+                                 "dense weights' update alone and must be 'sgd' or 'rwsadagrad'")
         if self.emb_precision == "fp16":
+            # the section that has this mode's limits (an explicit emb_optimizer: §26)
+            sec = "DESIGN.md §18" if self.emb_optimizer is None else "DESIGN.md §26"
             if self.optimizer == "adagrad":
                 raise NotImplementedError(
                     "emb_precision='fp16' with optimizer='adagrad': the element-wise Adagrad "
-                    "update takes fp32 tables and an fp32 accumulator (DESIGN.md §22)")
-            if self.optimizer == "rwsadagrad":
+                    "update takes fp32 tables and an fp32 accumulator (DESIGN.md §22; the fp16 "
+                    "tables' Adagrad is row-wise, emb_optimizer='rwsadagrad': DESIGN.md §26)")
+            if self.emb_optimizer is None and self.optimizer == "rwsadagrad":
                 raise NotImplementedError(
                     "emb_precision='fp16' with optimizer='rwsadagrad': there is no fp16 "
                     "row-wise Adagrad kernel (the reference's fp16 tables are EXACT_SGD only; "
-                    "DESIGN.md §18)")
+                    "DESIGN.md §18) behind optimizer= alone; set emb_optimizer='rwsadagrad' "
+                    "for the fp16 rows' row-wise Adagrad (DESIGN.md §26)")
             if self.qr_flag:
                 raise NotImplementedError(
                     "emb_precision='fp16' with qr_flag: the QR combine runs on fp32 tables "
-                    "only (DESIGN.md §18)")
+                    f"only ({sec})")
             if int(self.m_spa) % 4 or int(self.m_spa) > 512:
                 raise NotImplementedError(
                     f"emb_precision='fp16' with m_spa={self.m_spa}: the fp16 lookup takes D a "
-                    "multiple of 4 and at most 512 (dlrm_tbe_forward_rows; DESIGN.md §18)")
+                    f"multiple of 4 and at most 512 (dlrm_tbe_forward_rows; {sec})")
 
 
 @dataclass
@@ -224,7 +247,7 @@ class DLRMTrainer:
         if self.emb_f16 and (world_size > 1 or force_dist):
             raise NotImplementedError(
                 "emb_precision='fp16' on the multi-GPU schedule: the fp16 tables run on one "
-                "GPU only (DESIGN.md §18)")
+                "GPU only (DESIGN.md " + ("§18" if cfg.emb_optimizer is None else "§26") + ")")
         self.dev = torch.device(device)
         self.rank, self.world = rank, world_size
         self.pg = process_group
@@ -307,15 +330,15 @@ class DLRMTrainer:
         self._mlp8 = None
         self.momentum = None
         self.emb_sum = None
-        if cfg.optimizer == "rwsadagrad":
+        if cfg.optimizer not in ("sgd", "rwsadagrad", "adagrad"):
+            raise ValueError(f"optimizer {cfg.optimizer!r} not supported")
+        if cfg.emb_opt == "rwsadagrad":
             self.momentum = torch.zeros(max(self.total_rows, 1), dtype=torch.float32,
                                         device=self.dev)
-        elif cfg.optimizer == "adagrad":
+        elif cfg.emb_opt == "adagrad":
             # torch.optim.Adagrad's state['sum'] of the tables: one accumulator per weight
             self.emb_sum = torch.zeros((max(self.total_rows, 1), D), dtype=torch.float32,
                                        device=self.dev)
-        elif cfg.optimizer != "sgd":
-            raise ValueError(f"optimizer {cfg.optimizer!r} not supported")
         # ---- dense parameters: one flat bucket
         ln_bot, ln_top = [int(v) for v in cfg.ln_bot], [int(v) for v in cfg.ln_top]
         if ln_top[-1] != 1:
@@ -929,8 +952,8 @@ class DLRMTrainer:
         pool = (presort or not train) and not dist and not gather and self._pool_applies(batch)
         # fp16 tables (cfg.emb_precision): the same pieces on the fp16 row buffer - the
         # gather-fused interaction reads half rows, the pooled lookup is dlrm_tbe_forward_rows
-        # and the update MODE_SGD_F16 as launches of its own (no fp16 launch role: tbe_role
-        # below is off for them)
+        # and the update MODE_SGD_F16 or, emb_optimizer "rwsadagrad", MODE_ADAGRAD_F16 (either
+        # store) as launches of its own (no fp16 launch role: tbe_role below is off for them)
         f16 = self.emb_f16
         # quantized tables (predict's emb_bits = 8 | 4, forward only): a switch beside f16 - the
         # gather-fused interaction reads the packed snapshot, the pooled lookup is
@@ -1471,8 +1494,8 @@ class DLRMTrainer:
             GEMM launches (None: it ran in full here)."""
             with prof("tbe_bwd"):
                 if self.T_local > 0:
-                    mode = "rowwise_adagrad" if cfg.optimizer == "rwsadagrad" else "sgd"
-                    if f16:
+                    mode = "rowwise_adagrad" if cfg.emb_opt == "rwsadagrad" else "sgd"
+                    if f16 and mode == "sgd":  # (row-wise Adagrad: ops picks the fp16 entry)
                         mode = "sgd_f16"
                     emb_state = self.momentum
                     if self.emb_sum is not None:

@@ -156,8 +156,11 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  * 22: the 16-bit Linear backward as a grouped launch: dlrm_linear16_bwd_problem /
  *    dlrm_linear16_bwd_group (+ _workspace_size): up to four independent dgrads / wgrads of
  *    ABI v13 in one launch, split wgrads folded inside it by the last-arriving workgroup of a
- *    tile (no reduce launch); the bits of dlrm_linear16_dgrad / dlrm_linear16_wgrad. */
-#define DLRM_ABI_VERSION 22/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
+ *    tile (no reduce launch); the bits of dlrm_linear16_dgrad / dlrm_linear16_wgrad.
+ * 23: row-wise Adagrad on fp16 embedding rows: dlrm_tbe_backward_rowwise_adagrad_f16 (fp32
+ *    momentum and arithmetic, the row widened on load and stored to nearest even or, with an
+ *    sr_state, stochastically; host or device rate). */
+#define DLRM_ABI_VERSION 23/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
 const char* dlrm_last_error(void);
@@ -1263,6 +1266,40 @@ int dlrm_tbe_backward_adagrad(float* weights, float* state_sum, int64_t D,
                               float eps, int64_t max_lookups_per_table, void* workspace,
                               size_t workspace_bytes, int32_t* error_flag, int32_t presorted,
                               dlrm_stream_t stream);
+/*
+ * Row-wise Adagrad on fp16 rows (ABI v23; fbgemm's EXACT_ROWWISE_ADAGRAD on FP16 tables).
+ * weights is [total_rows, D] fp16, momentum [total_rows] fp32.  The sort, the run order and the
+ * Kahan-compensated sums are dlrm_tbe_backward_rowwise_adagrad's; then, for every unique row r
+ * the call touches, with g the coalesced gradient:
+ *   sq    = sum_d g[d]^2           (the lane partials and shuffle order of the fp32-row kernel)
+ *   mnew  = momentum[r] + sq / (float)D;   momentum[r] = mnew
+ *   denom = sqrtf(mnew) + eps
+ *   v[d]  = fmaf(-lr, g[d] / denom, (float)weights[r, d])              (fp32)
+ *   weights[r, d] = half_rne(v[d])                                     sr_state == NULL
+ *   weights[r, d] = sr16(v[d], r16(r, d))                              sr_state != NULL
+ * sr16 and r16 are dlrm_tbe_backward_sgd_f16_sr's rule and stream (same key, one word per four
+ * columns, the global row); the state is read when the kernels run and never written.  v and
+ * mnew are, bit for bit, what dlrm_tbe_backward_rowwise_adagrad computes on an fp32 table
+ * holding the widened halves: only the row load and the row store differ.
+ *
+ * lr_dev == NULL: the host `lr` is used; else the device fp32 replaces it.  A NULL momentum or
+ * a misaligned (not 8-byte) sr_state is DLRM_ERR_INVALID_ARG, a D beyond the lane ladder
+ * DLRM_ERR_UNSUPPORTED, as for the sibling entry points.  Four-column lanes need D % 4 == 0
+ * and 8-byte aligned rows; otherwise the scalar lanes run (same result).  The update is not a
+ * launch role.
+ */
+int dlrm_tbe_backward_rowwise_adagrad_f16(void* weights, float* momentum, int64_t D,
+                                          const int64_t* row_base, int32_t T, int32_t B,
+                                          const void* indices, int32_t index_bits,
+                                          const void* offsets, int32_t offset_bits,
+                                          int64_t num_lookups, int64_t total_rows,
+                                          const float* per_sample_weights,
+                                          const float* grad_out, int64_t grad_batch_stride,
+                                          float lr, const float* lr_dev, float eps,
+                                          const uint64_t* sr_state,
+                                          int64_t max_lookups_per_table, void* workspace,
+                                          size_t workspace_bytes, int32_t* error_flag,
+                                          int32_t presorted, dlrm_stream_t stream);
 int dlrm_tbe_backward_rowwise_adagrad_dev(float* weights, float* momentum, int64_t D,
                                           const int64_t* row_base, int32_t T, int32_t B,
                                           const void* indices, int32_t index_bits,

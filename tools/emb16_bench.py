@@ -12,6 +12,10 @@ measures the fp32 default and is not touched):
           stored rounded to "nearest" (the mode as it was) against "stochastic"
           (TrainerConfig.emb_rounding: the hash and one more one-thread launch per step);
           training step only, written to profiles/sr16_bench.json.
+          --adagrad: three trainers with optimizer="rwsadagrad" - fp32 tables (the update a
+          launch role), fp16 tables with emb_optimizer="rwsadagrad" (the update
+          as launches of its own) and the same with the stochastic store; training step only,
+          written to profiles/adagrad16_bench.json.
   trace : --steps replays of the fp16-table step and nothing else, to run under
           `rocprofv3 --kernel-trace` (tools/step_timeline.py prints one step of the trace).
   ab    : the fp32 default of this tree against a built checkout of the parent commit
@@ -19,7 +23,7 @@ measures the fp32 default and is not touched):
           fresh processes; the parent's numbers and every loss_last are written down.
 
 Writes one JSON document to --out and prints it.
-python tools/emb16_bench.py step [--config terabyte] [--steps 200] [--rounds 3] [--rounding]
+python tools/emb16_bench.py step [--config terabyte] [--steps 200] [--rounds 3] [--rounding | --adagrad]
 python tools/emb16_bench.py trace [--config terabyte] [--steps 30]
 python tools/emb16_bench.py ab --parent DIR [--steps 300] [--warmup 50] [--rounds 3]"""
 import argparse
@@ -36,6 +40,8 @@ from lr_sched_bench import _stats, _time_ms, ab  # noqa: E402
 
 MODES = ("fp32", "fp16")
 ROUNDINGS = ("nearest", "stochastic")  # step --rounding: both on fp16 tables
+# step --adagrad: row-wise Adagrad on fp32 tables, on fp16 tables, and with the stochastic store
+ADAGRAD = ("rws_fp32", "rws_fp16", "rws_fp16_sr")
 NB = 10  # batches a window cycles through
 
 
@@ -48,10 +54,15 @@ def _trainer(config, dev, mode):
     c = bench.CONFIGS[config]
     if c.get("qr") is not None or c["optimizer"] != "sgd":
         raise SystemExit(f"config {config}: fp16 tables run plain tables with SGD only")
+    kw.setdefault("optimizer", c["optimizer"])
+    if mode in ADAGRAD:
+        kw = dict(optimizer="rwsadagrad")
+        if mode != "rws_fp32":
+            kw.update(emb_precision="fp16", emb_optimizer="rwsadagrad",
+                      emb_rounding="stochastic" if mode == "rws_fp16_sr" else "nearest")
     cfg = TrainerConfig(m_spa=c["D"], ln_emb=c["rows"], ln_bot=c["bot"],
                         ln_top=[bench.num_int(len(c["rows"]), c["D"])] + c["top"],
-                        loss_function=c["loss"], learning_rate=c["lr"], optimizer=c["optimizer"],
-                        **kw)
+                        loss_function=c["loss"], learning_rate=c["lr"], **kw)
     return c, DLRMTrainer(cfg, device=dev, seed=1)
 
 
@@ -91,10 +102,11 @@ def step(args):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     pool = torch.cuda.graph_pool_handle()
-    MODES = ROUNDINGS if args.rounding else globals()["MODES"]
-    base, other = MODES
-    kinds = (("train", 2),) if args.rounding else (("train", 2), ("predict", 3))
-    runs = {m: _captured(args.config, dev, m, pool, not args.rounding) for m in MODES}
+    train_only = args.rounding or args.adagrad
+    MODES = ADAGRAD if args.adagrad else ROUNDINGS if args.rounding else globals()["MODES"]
+    base = MODES[0]
+    kinds = (("train", 2),) if train_only else (("train", 2), ("predict", 3))
+    runs = {m: _captured(args.config, dev, m, pool, not train_only) for m in MODES}
     c = runs[base][0]
     bench.preheat_device(dev, 300.0)
     win = {kind: {m: [] for m in MODES} for kind, _ in kinds}
@@ -111,13 +123,17 @@ def step(args):
            "gather_fused": {m: bool(runs[m][1].gather_fused) for m in MODES}}
     for kind in win:
         row = {m: _stats(w) for m, w in win[kind].items()}
-        a, h = row[base], row[other]
-        row[f"{other}_over_{base}"] = round(h["median"] / a["median"], 4)
-        row[f"{other}_minus_{base}_us"] = round((h["median"] - a["median"]) * 1000.0, 2)
-        row["outside_spread"] = bool(abs(h["median"] - a["median"]) > max(a["spread"], h["spread"]))
+        a = row[base]
+        for other in MODES[1:]:
+            h = row[other]
+            row[f"{other}_over_{base}"] = round(h["median"] / a["median"], 4)
+            row[f"{other}_minus_{base}_us"] = round((h["median"] - a["median"]) * 1000.0, 2)
+            outside = bool(abs(h["median"] - a["median"]) > max(a["spread"], h["spread"]))
+            row["outside_spread" if len(MODES) == 2 else f"{other}_outside_spread"] = outside
         res["ms_per_" + kind] = row
-    if args.rounding:
-        res["rounding_state"] = list(runs["stochastic"][1].rounding_state())
+    if train_only:
+        sr = MODES[-1]
+        res["rounding_state"] = list(runs[sr][1].rounding_state())
     return res
 
 
@@ -144,6 +160,8 @@ def main():
     s.add_argument("--rounds", type=int, default=3)
     s.add_argument("--rounding", action="store_true",
                    help="fp16 tables: emb_rounding nearest against stochastic")
+    s.add_argument("--adagrad", action="store_true",
+                   help="row-wise Adagrad: fp32 tables against fp16 tables, either store")
     s.add_argument("--out", default=None)
     t = sub.add_parser("trace")
     t.add_argument("--config", default="terabyte")
@@ -158,6 +176,7 @@ def main():
     args = ap.parse_args()
     if args.cmd == "step" and args.out is None:
         args.out = os.path.join(ROOT, "profiles",
+                                "adagrad16_bench.json" if args.adagrad else
                                 "sr16_bench.json" if args.rounding else "emb16_bench.json")
     res = {"step": step, "trace": trace, "ab": ab}[args.cmd](args)
     if args.out:
