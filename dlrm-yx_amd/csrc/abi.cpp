@@ -66,6 +66,12 @@ namespace {
                                              const uint64_t*, int64_t, void*, size_t, int32_t*,
                                              int32_t,
                                              dlrm_stream_t) = &dlrm_tbe_backward_rowwise_adagrad_f16;
+[[maybe_unused]] int (*const kLinear16Pack)(int32_t, int64_t, int64_t, const float*, int64_t, void*,
+                                            int64_t, dlrm_stream_t) = &dlrm_linear16_pack;
+[[maybe_unused]] int (*const kLinear16Packed)(int32_t, int64_t, int64_t, int64_t, const void*,
+                                              int32_t, int64_t, const void*, int64_t,
+                                              const float*, int64_t, int32_t, void*, int32_t,
+                                              int64_t, dlrm_stream_t) = &dlrm_linear16_forward_packed;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

@@ -267,6 +267,12 @@ SIGNATURES = {
                                                         c_int32, P, c_int32, c_int64, c_int64, P,
                                                         P, c_int64, c_float, P, c_float, P,
                                                         c_int64, P, c_size_t, P, c_int32, P]),
+    # added to ABI v23 without a new number (load() names a missing one): 16-bit MLP operands
+    # in memory (the weight packer; the Linear on the packed image with an fp32 or 16-bit X, Y)
+    "dlrm_linear16_pack": (c_int32, [c_int32, c_int64, c_int64, P, c_int64, P, c_int64, P]),
+    "dlrm_linear16_forward_packed": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
+                                               c_int64, P, c_int64, P, c_int64, c_int32, P,
+                                               c_int32, c_int64, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}
@@ -291,7 +297,11 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} has ABI version {got}, the bindings expect {ABI_VERSION}; rebuild it "
             f"with `make -C dlrm-yx_amd/csrc`")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # an older build of the same ABI number
+            raise DLRMHipUnavailable(
+                f"{LIB_PATH} lacks {name}; rebuild it with `make -C dlrm-yx_amd/csrc`") from None
         fn.restype = res
         fn.argtypes = args
     _lib = lib

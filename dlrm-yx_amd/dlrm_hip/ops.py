@@ -1129,6 +1129,115 @@ def mlp_chain16_forward(chain, device=None) -> None:
               _stream(dev))
 
 
+TORCH16 = {"bf16": torch.bfloat16, "fp16": torch.float16}
+L16_FP32, L16_HALF = 0, 1  # dlrm_linear16_kind
+
+
+class Linear16Weights:
+    """The packed weights of one 16-bit Linear (dlrm_linear16_pack): ``wp`` [N, ldwp] of
+    ``dtype`` ("bf16" | "fp16") with ldwp a multiple of 64 (columns >= K are 0), on the device
+    of the fp32 weights."""
+
+    def __init__(self, wp: torch.Tensor, N: int, K: int, dtype: str):
+        if dtype not in MLP16_TYPES:
+            raise ValueError(f"Linear16Weights: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+        if wp.dtype != TORCH16[dtype] or wp.dim() != 2 or not wp.is_contiguous() \
+                or wp.shape[0] != N or wp.shape[1] % 64 or wp.shape[1] < max(K, 64):
+            raise ValueError(f"Linear16Weights: wp must be contiguous {dtype} [{N}, ldwp] with "
+                             f"ldwp a multiple of 64 and >= {max(K, 64)}, not {wp.dtype} "
+                             f"{list(wp.shape)}")
+        self.wp, self.N, self.K, self.dtype = wp, int(N), int(K), dtype
+
+
+def linear16_pack(W: torch.Tensor, dtype: str = "bf16",
+                  out: Optional[Linear16Weights] = None) -> Linear16Weights:
+    """dlrm_linear16_pack: W [N, K] fp32 (a view with contiguous rows: the columns past K of a
+    wider buffer, e.g. a folded bias column, are not read) -> the nearest-even ``dtype`` image
+    linear16_forward_packed reads, bitwise W.to(dtype) in columns < K and zero past them.
+    ``out``: a Linear16Weights of the same N, K and dtype to re-pack into (its storage is
+    kept)."""
+    if dtype not in MLP16_TYPES:
+        raise ValueError(f"linear16_pack: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
+    ldw = _row_major(W, "W", "linear16_pack")
+    _check_cuda(W)
+    N, K = W.shape
+    if out is None:
+        ldwp = max((K + 63) // 64 * 64, 64)
+        out = Linear16Weights(torch.zeros((N, ldwp), dtype=TORCH16[dtype], device=W.device),
+                              N, K, dtype)
+    elif not isinstance(out, Linear16Weights) or (out.N, out.K, out.dtype) != (N, K, dtype) \
+            or out.wp.device != W.device:
+        raise ValueError(f"linear16_pack: out does not hold [{N}, {K}] {dtype} weights on "
+                         f"{W.device}")
+    _lib.call("dlrm_linear16_pack", MLP16_TYPES[dtype], N, K, _p(W), ldw, _p(out.wp),
+              out.wp.shape[1], _stream(W.device))
+    return out
+
+
+def _row_major16(t: torch.Tensor, dtype: str, what: str, fn: str):
+    """(kind, leading dimension) of a 2-D fp32 or ``dtype`` tensor whose rows are contiguous;
+    a 16-bit one must be 16-byte aligned with a row stride that is a multiple of 8."""
+    if t.dim() != 2 or t.dtype not in (torch.float32, TORCH16[dtype]) \
+            or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{fn}: {what} must be 2-D fp32 or {dtype} with contiguous rows")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], 1)
+    if t.dtype == torch.float32:
+        return L16_FP32, ld
+    if t.shape[0] <= 1:
+        ld = (ld + 7) // 8 * 8
+    if ld % 8 or (t.numel() and t.data_ptr() % 16):
+        raise ValueError(f"{fn}: a {dtype} {what} must be 16-byte aligned with a row stride "
+                         f"that is a multiple of 8 (stride {ld})")
+    return L16_HALF, ld
+
+
+def linear16_forward_packed(x: torch.Tensor, packed: Linear16Weights,
+                            bias: Optional[torch.Tensor] = None, relu: bool = False,
+                            out: Optional[torch.Tensor] = None,
+                            out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Forward-only Linear on the 16-bit MFMA with the weights packed in memory
+    (dlrm_linear16_forward_packed): out [M, N] = act(r16(x) Wp^T + bias).  ``x`` [M, K]: an
+    fp32 tensor or view with contiguous rows (rounded in flight, as linear16_forward does) or
+    one of the packed dtype (torch.bfloat16 / torch.float16; K and the row stride multiples of
+    8, 16-byte aligned), used as it is.  ``out`` / ``out_dtype``: fp32 (the default) or the
+    packed dtype, which stores the result rounded to nearest even (row stride a multiple of 8,
+    16-byte aligned; N may be any size).  The fp32 result is bit for bit
+    linear16_forward(x32, W, ...) under the same tile, x32 the fp32 tensor a 16-bit x was
+    rounded from.  ``bias`` may be a strided 1-D fp32 view; only out[:M, :N] is written."""
+    fn = "linear16_forward_packed"
+    if not isinstance(packed, Linear16Weights):
+        raise ValueError(f"{fn}: packed must be a Linear16Weights (linear16_pack)")
+    dt = packed.dtype
+    x_kind, ldx = _row_major16(x, dt, "x", fn)
+    M, K = x.shape
+    N = packed.N
+    if K != packed.K:
+        raise ValueError(f"{fn}: x is [{M}, {K}], the packed weights are [{N}, {packed.K}]")
+    if x_kind == L16_HALF and K % 8:
+        raise ValueError(f"{fn}: a {dt} x needs K a multiple of 8, not {K}")
+    bstride = 0
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != N or bias.dtype != torch.float32:
+            raise ValueError(f"{fn}: bias must be N fp32 values")
+        bstride = bias.stride(0) if N > 1 else 1
+    if out is not None and out_dtype is not None and out.dtype != out_dtype:
+        raise ValueError(f"{fn}: out is {out.dtype}, out_dtype {out_dtype}")
+    want = out.dtype if out is not None else (out_dtype or torch.float32)
+    if want not in (torch.float32, TORCH16[dt]):
+        raise ValueError(f"{fn}: the output must be fp32 or {dt}, not {want}")
+    _check_cuda(x, packed.wp, bias, out)
+    if out is None:
+        ldo = N if want == torch.float32 else (N + 7) // 8 * 8
+        out = torch.empty((M, ldo), dtype=want, device=x.device)[:, :N]
+    if out.dim() != 2 or tuple(out.shape) != (M, N):
+        raise ValueError(f"{fn}: out is {list(out.shape)}, expected [{M}, {N}]")
+    y_kind, ldy = _row_major16(out, dt, "out", fn)
+    _lib.call("dlrm_linear16_forward_packed", MLP16_TYPES[dt], M, N, K, _p(x), x_kind, ldx,
+              _p(packed.wp), packed.wp.shape[1], _p(bias), bstride, int(bool(relu)), _p(out),
+              y_kind, ldy, _stream(x.device))
+    return out
+
+
 LINEAR8_TILES = LINEAR16_TILES  # DLRM_TUNE_LINEAR8_TILE values
 LINEAR8_RANGE_FLOATS = 2048  # DLRM_LINEAR8_RANGE_FLOATS: min partials, then max partials
 LINEAR8_MAX_K = 131072

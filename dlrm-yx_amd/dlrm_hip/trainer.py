@@ -233,6 +233,13 @@ class _Layer8:
     rng: torch.Tensor   # the min / max partials of this layer's input, rewritten by every call
 
 
+@dataclass
+class _Layer16:
+    """pack_mlp16's snapshot of one layer below the head."""
+    packed: "ops.Linear16Weights"  # the 16-bit image of W[:, :K]
+    bias: torch.Tensor  # [N] fp32 copy
+
+
 class DLRMTrainer:
     def __init__(self, cfg: TrainerConfig, device="cuda:0", rank: int = 0, world_size: int = 1,
                  process_group=None, seed: int = 0, init: bool = True, comm=None,
@@ -328,6 +335,9 @@ class DLRMTrainer:
         # the int8 snapshot of the MLP layers for predict(mlp_bits=8), filled by quantize_mlp
         # (DESIGN.md §21): id(layer) -> _Layer8; the training step never reads it
         self._mlp8 = None
+        # the 16-bit snapshots of the MLP layers below the head for predict(mlp_store=16), one
+        # per dtype, filled by pack_mlp16
+        self._mlp16 = {}
         self.momentum = None
         self.emb_sum = None
         if cfg.optimizer not in ("sgd", "rwsadagrad", "adagrad"):
@@ -913,7 +923,7 @@ class DLRMTrainer:
 
     def _build(self, batch: Batch, profile=None, predict=None):
         """The segment list of the training step (segments) or, ``predict`` = (metrics,
-        precision, emb_bits, mlp_bits), of the forward-only pass (predict_segments), from one set of pieces: the
+        precision, emb_bits, mlp_bits, mlp_store), of the forward-only pass (predict_segments), from one set of pieces: the
         context of this call first, then the pieces both lists use, the forward-only list,
         the pieces of the backward and the step's four segment orders.
 
@@ -922,11 +932,14 @@ class DLRMTrainer:
         layer and pass.  Every other piece is the same code for both."""
         cfg = self.cfg
         train = predict is None
-        metrics, precision, emb_bits, mlp_bits = \
-            (None, cfg.mlp_precision, 32, 32) if train else predict
+        metrics, precision, emb_bits, mlp_bits, mlp_store = \
+            (None, cfg.mlp_precision, 32, 32, 32) if train else predict
         # predict's mlp_bits = 8 (DESIGN.md §21): like the 16-bit modes it selects only the MLP
         # closures below and runs without the fused bottom chain
         q8 = None if mlp_bits == 32 else self.quantized_mlp(mlp_bits)
+        # predict's mlp_store = 16 (DESIGN.md §27): the 16-bit closure below on pack_mlp16's
+        # snapshot, per-layer launches (no bottom chain)
+        p16 = None if mlp_store == 32 else self.packed_mlp16(precision)
         fp32 = precision == "fp32" and q8 is None
         D = self.D
         Bl = batch.X.shape[0]
@@ -1012,7 +1025,7 @@ class DLRMTrainer:
 
         # a training step keeps every layer's activations for the backward; predict only the last
         chain16 = self._bottom_chain16(batch, bufs, precision, keep=train) \
-            if self.fuse_bottom16 and not fp32 and q8 is None else None
+            if self.fuse_bottom16 and not fp32 and q8 is None and p16 is None else None
         self.bottom16_fused = chain16 is not None
 
         if fp32:
@@ -1029,6 +1042,20 @@ class DLRMTrainer:
                     ops.linear8_range(h[:, :L.K], out=s.rng)
                     ops.linear8_forward(h[:, :L.K], s.packed, bias=s.bias, relu=relu,
                                         out=out[:, :L.N], rng=s.rng)
+        elif p16 is not None:
+            # 16 bit, packed: the same launch count and the same bits as the closure below, on
+            # the snapshot's 16-bit weight image; the buffer between two Linear layers of one
+            # MLP is a 16-bit one of its own (r16(y), what the next layer would round on load)
+            # where its width is a multiple of 8.  The boundaries the fp32 kernels own (dense
+            # input, interaction input and output, the head's input) stay the fp32 buffers.
+            half = self._act16(ws, bufs, precision)
+
+            def mlp_fwd(L, h, out, side=False):
+                with prof("gemm"):
+                    s, src, dst = p16[id(L)], half.get(id(h)), half.get(id(out))
+                    ops.linear16_forward_packed(h[:, :L.K] if src is None else src, s.packed,
+                                                bias=s.bias, relu=True,
+                                                out=out[:, :L.N] if dst is None else dst)
         else:
             # 16 bit: one launch, relu(r16(h[:, :K]) r16(W[:, :K])^T + b) -> out[:, :N], the
             # operands rounded to nearest-even in flight from the fp32 tensors (no weight
@@ -1940,6 +1967,72 @@ class DLRMTrainer:
             raise RuntimeError("no int8 MLP layers: call quantize_mlp(8) first")
         return self._mlp8
 
+    def pack_mlp16(self, dtype: str) -> None:
+        """Round every Linear of the bottom and top MLP below the head once into a 16-bit
+        image (``dtype`` "bf16" | "fp16": dlrm_linear16_pack, the bias column left out) and
+        copy its bias, in engine-owned buffers that predict(..., precision=dtype,
+        mlp_store=16) reads instead of the fp32 masters.
+
+        A SNAPSHOT, as quantize_mlp's: the fp32 masters stay, training is untouched and does
+        not move the packed layers; a second call re-packs into the same storage, so an
+        already captured predict graph reads the new values.  One snapshot per dtype."""
+        if dtype not in ops.MLP16_TYPES:
+            raise ValueError(f"pack_mlp16({dtype!r}): 'bf16' or 'fp16'")
+        self._mlp16_refusals()
+        snap = self._mlp16.setdefault(dtype, {})
+        for L in self.bot + self.top[:-1]:
+            s = snap.get(id(L))
+            if s is None:
+                snap[id(L)] = _Layer16(packed=ops.linear16_pack(L.W[:, :L.K], dtype),
+                                       bias=L.b.clone())
+            else:
+                ops.linear16_pack(L.W[:, :L.K], dtype, out=s.packed)
+                s.bias.copy_(L.b)
+
+    def _mlp16_refusals(self) -> None:
+        if self.distributed:
+            raise NotImplementedError(
+                "pack_mlp16 / mlp_store=16 on the multi-GPU schedule: the packed 16-bit MLP "
+                "layers run on one GPU only (DESIGN.md §27)")
+
+    def packed_mlp16(self, dtype: str) -> dict:
+        """The packed layers of pack_mlp16(dtype), keyed by id(layer)."""
+        if dtype not in self._mlp16:
+            raise RuntimeError(f"no packed {dtype} MLP layers: call pack_mlp16({dtype!r}) first")
+        return self._mlp16[dtype]
+
+    def _mlp_store(self, mlp_store: int, precision: str, mlp_bits: int) -> int:
+        """Validate predict's ``mlp_store``: 32 = fp32 weights and activations in memory, 16 =
+        the snapshot of pack_mlp16(precision) and 16-bit buffers between the layers (16-bit
+        ``precision``, ``mlp_bits`` 32, one GPU, and the snapshot must exist)."""
+        if mlp_store == 32:
+            return 32
+        if mlp_store != 16:
+            raise ValueError(f"mlp_store {mlp_store!r}: 32 or 16")
+        if precision not in ops.MLP16_TYPES:
+            raise ValueError(f"mlp_store=16 with precision={precision!r}: pack_mlp16 stores "
+                             "'bf16' or 'fp16' operands; pass that dtype as precision")
+        if mlp_bits != 32:
+            raise ValueError(f"mlp_store=16 with mlp_bits={mlp_bits!r}: pack_mlp16's layers and "
+                             "quantize_mlp's exclude each other; leave mlp_bits at 32")
+        self._mlp16_refusals()
+        self.packed_mlp16(precision)
+        return 16
+
+    def _act16(self, pb, bufs, dtype: str) -> dict:
+        """mlp_store = 16: the 16-bit buffer that stands for an fp32 activation buffer, keyed
+        by id(that buffer) - one per output of a Linear that feeds the next Linear of the same
+        MLP and whose width is a multiple of 8 (a 16-bit row must keep 16-byte chunks)."""
+        key = ("act16", dtype)
+        if key not in pb:
+            pb[key] = {
+                id(out): torch.zeros((out.shape[0], L.N), dtype=ops.TORCH16[dtype],
+                                     device=self.dev)
+                for layers, outs in ((self.bot, bufs["bot_act"]),
+                                     (self.top[:-1], bufs["top_act"]))
+                for L, out in list(zip(layers, outs))[:-1] if L.N % 8 == 0}
+        return pb[key]
+
     def _mlp_bits(self, mlp_bits: int, precision: str) -> int:
         """Validate predict's ``mlp_bits``: 32 = the ``precision`` path, 8 = the packed
         snapshot of quantize_mlp(8) (which must exist; fp32 ``precision`` only)."""
@@ -1955,7 +2048,7 @@ class DLRMTrainer:
         return 8
 
     def predict(self, batch: Batch, metrics=None, precision: str = "fp32",
-                emb_bits: int = 32, mlp_bits: int = 32) -> torch.Tensor:
+                emb_bits: int = 32, mlp_bits: int = 32, mlp_store: int = 32) -> torch.Tensor:
         """Forward only: prob [B_local] for ``batch`` (a device tensor owned by this batch
         size, overwritten by the next predict of it).  Writes no weight, no optimizer
         state, no gradient and no pending launch role; with ``metrics`` (a
@@ -1964,8 +2057,11 @@ class DLRMTrainer:
         (predict_segments).  ``emb_bits`` 8 | 4: the embedding rows from the packed snapshot
         of quantize_embedding(emb_bits) instead of the master tables.  ``mlp_bits`` 8: every
         MLP layer, the last one included, as a dynamically quantized int8 Linear on the
-        snapshot of quantize_mlp(8)."""
-        for _kind, fn in self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits):
+        snapshot of quantize_mlp(8).  ``mlp_store`` 16: the 16-bit ``precision`` path on the
+        packed snapshot of pack_mlp16(precision), bit for bit the ``precision`` path's result
+        on the weights that were packed."""
+        for _kind, fn in self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits,
+                                               mlp_store):
             fn()
         return self._predict_bufs(self._buffers(batch.X.shape[0],
                                                 batch.X.shape[0] * self.world))["prob"]
@@ -1987,7 +2083,7 @@ class DLRMTrainer:
         return pb
 
     def predict_segments(self, batch: Batch, metrics=None, precision: str = "fp32",
-                         emb_bits: int = 32, mlp_bits: int = 32):
+                         emb_bits: int = 32, mlp_bits: int = 32, mlp_store: int = 32):
         """The forward-only pass as ("gpu" | "a2a" | "host", fn) items, the form of
         ``segments()`` and built from the same pieces (_build): the lookup
         (dlrm_tbe_forward; nothing of the backward's sort), the bottom MLP (one GPU: beside
@@ -2017,53 +2113,68 @@ class DLRMTrainer:
         dynamically quantized nn.Linear; the last layer too, as N = 1 without ReLU, and
         dlrm_head_predict keeps the sigmoid, the clamp and the metric log.  The fused bottom
         chain is not used.  It needs ``precision`` "fp32" (ValueError otherwise), composes
+        with ``emb_bits`` and ``metrics``, and runs on one GPU only.
+
+        ``mlp_store`` 16: with ``precision`` "bf16" | "fp16", every layer
+        below the head runs as one dlrm_linear16_forward_packed launch on the 16-bit weight
+        image pack_mlp16(precision) built (RuntimeError without one) and the activation
+        between two Linear layers of one MLP is stored rounded, in a 16-bit buffer of its own,
+        where its width is a multiple of 8 - the operand bits the ``precision`` path rounds in
+        flight, so the result is that path's bit for bit (on the packed weights).  The fused
+        bottom chain is not used.  It needs ``mlp_bits`` 32 (ValueError otherwise), composes
         with ``emb_bits`` and ``metrics``, and runs on one GPU only."""
         return self._build(batch, predict=(metrics, _precision(precision),
                                            self._emb_bits(emb_bits),
-                                           self._mlp_bits(mlp_bits, precision)))
+                                           self._mlp_bits(mlp_bits, precision),
+                                           self._mlp_store(mlp_store, precision, mlp_bits)))
 
     def capture_predict(self, batch: Batch, metrics=None, pool=None, precision: str = "fp32",
-                        emb_bits: int = 32, mlp_bits: int = 32):
+                        emb_bits: int = 32, mlp_bits: int = 32, mlp_store: int = 32):
         """A replayable forward-only pass for ``batch`` (capture()'s modes over
         predict_segments).  Run one eager predict of this batch size first (allocations).
         Each call of the returned callable scores the batch's current contents into the
         tensor predict() returns; with ``metrics`` every call appends B_local samples (the
         log's cursor lives on the device).  ``precision``, ``emb_bits``: as predict_segments
         (the graph holds the packed buffer's address; quantize_embedding re-packs in place),
-        ``mlp_bits`` likewise (quantize_mlp re-packs in place)."""
+        ``mlp_bits`` likewise (quantize_mlp re-packs in place), and ``mlp_store``
+        (pack_mlp16 re-packs in place)."""
         _precision(precision)
         self._emb_bits(emb_bits)
         self._mlp_bits(mlp_bits, precision)
+        self._mlp_store(mlp_store, precision, mlp_bits)
         run, _mode, _graphs = self._capture_segments(
-            lambda: self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits),
+            lambda: self.predict_segments(batch, metrics, precision, emb_bits, mlp_bits,
+                                          mlp_store),
             pool, None)
         return run
 
     def evaluate(self, batches, metrics, precision: str = "fp32", emb_bits: int = 32,
-                 mlp_bits: int = 32) -> dict:
+                 mlp_bits: int = 32, mlp_store: int = 32) -> dict:
         """Score every batch into ``metrics`` (a metrics.EvalState, not reset here) and
         return its compute() dict (on several ranks: over all ranks' samples).  One graph
         per batch shape - a smaller last batch gets its own - replayed on fixed buffers the
         batches are copied into.  Index errors are checked once, at the end.
-        ``precision``, ``emb_bits``, ``mlp_bits``: as predict_segments (parts of the graph
-        key)."""
+        ``precision``, ``emb_bits``, ``mlp_bits``, ``mlp_store``: as predict_segments (parts
+        of the graph key)."""
         _precision(precision)
         self._emb_bits(emb_bits)
         self._mlp_bits(mlp_bits, precision)
+        self._mlp_store(mlp_store, precision, mlp_bits)
         graphs = {}
         for batch in batches:
             key = (batch.X.shape[0], batch.indices.numel(), batch.offsets.numel(),
                    self._gather_applies(batch), self._pool_applies(batch), precision, emb_bits,
-                   mlp_bits)
+                   mlp_bits, mlp_store)
             if key not in graphs:
                 fixed = Batch(batch.X.clone(), batch.offsets.clone(), batch.indices.clone(),
                               batch.target.clone(), batch.max_per_table, batch.one_hot)
-                self.predict(fixed, precision=precision, emb_bits=emb_bits,
-                             mlp_bits=mlp_bits)  # eager, unlogged: allocations
+                self.predict(fixed, precision=precision, emb_bits=emb_bits, mlp_bits=mlp_bits,
+                             mlp_store=mlp_store)  # eager, unlogged: allocations
                 torch.cuda.current_stream(self.dev).synchronize()
                 graphs[key] = (fixed, self.capture_predict(fixed, metrics, precision=precision,
                                                            emb_bits=emb_bits,
-                                                           mlp_bits=mlp_bits))
+                                                           mlp_bits=mlp_bits,
+                                                           mlp_store=mlp_store))
             fixed, run = graphs[key]
             fixed.X.copy_(batch.X)
             fixed.offsets.copy_(batch.offsets)

@@ -159,7 +159,13 @@ enum dlrm_qr_op { DLRM_QR_MULT = 0, DLRM_QR_ADD = 1, DLRM_QR_CONCAT = 2 };
  *    tile (no reduce launch); the bits of dlrm_linear16_dgrad / dlrm_linear16_wgrad.
  * 23: row-wise Adagrad on fp16 embedding rows: dlrm_tbe_backward_rowwise_adagrad_f16 (fp32
  *    momentum and arithmetic, the row widened on load and stored to nearest even or, with an
- *    sr_state, stochastically; host or device rate). */
+ *    sr_state, stochastically; host or device rate).
+ * 23, added without a new number (two new entry points, nothing existing changes, so every
+ *    caller of v23 runs unchanged; the bindings refuse a library that lacks them by name):
+ *    16-bit MLP operands in memory for inference: dlrm_linear16_pack (the fp32 weights
+ *    rounded once into a zero-padded bf16 / fp16 image) and dlrm_linear16_forward_packed (the
+ *    Linear of ABI v12 reading that image and an fp32 or 16-bit X, writing an fp32 or 16-bit
+ *    Y; the bits of dlrm_linear16_forward). */
 #define DLRM_ABI_VERSION 23/* the one source of truth: abi.cpp returns it, dlrm_hip/_lib.py
                              pins it (tests/test_cpu_host.py checks all of them agree) */
 int dlrm_abi_version(void);
@@ -188,7 +194,8 @@ const char* dlrm_last_error(void);
  *                          for batches <= 1024)
  *                          (ABI v7)
  *   DLRM_TUNE_LINEAR16_TILE : BM * 1000 + BN of dlrm_linear16_forward's workgroup tile
- *                          (128128, 128064, 64064, 32064) (ABI v12)
+ *                          (128128, 128064, 64064, 32064) (ABI v12), and of
+ *                          dlrm_linear16_forward_packed's (ABI v23, added)
  *   DLRM_TUNE_LINEAR16_DGRAD_TILE / DLRM_TUNE_LINEAR16_WGRAD_TILE : the same four values
  *                          for dlrm_linear16_dgrad (tile of dX, M x K) and
  *                          dlrm_linear16_wgrad (tile of C, N x K) (ABI v13)
@@ -1012,6 +1019,47 @@ typedef struct dlrm_mlp_chain16 {
 /* 1 when dlrm_mlp_chain16_forward can take this chain, else 0. */
 int dlrm_mlp_chain16_supported(const dlrm_mlp_chain16* chain);
 int dlrm_mlp_chain16_forward(const dlrm_mlp_chain16* chain, dlrm_stream_t stream);
+
+/*
+ * The same Linear with 16-bit operands IN MEMORY (added to ABI v23): weights that do not change
+ * between inference steps are rounded once, and an activation that is only ever consumed as a
+ * rounded operand is stored rounded.
+ *
+ * dlrm_linear16_pack: Wp[n][k] = r16(W[n][k]) for k < K, 0 for K <= k < ldwp, n < N.  W is
+ * fp32 [N][K] with row stride ldw (columns >= K of a wider buffer, e.g. a folded bias column,
+ * are not read); r16 is dlrm_linear16_forward's round-to-nearest-even cast to `type`.  Wp is
+ * 16-byte aligned, ldwp (elements) a multiple of 64 and >= max(K, 64), else DLRM_ERR_SHAPE.
+ * One pass, 16-byte stores, no workspace; packing again into the same Wp is how a snapshot is
+ * refreshed.  N == 0: nothing to do.
+ *
+ * dlrm_linear16_forward_packed:
+ *   Y[m][n] = act( sum_{k<K} r16(X[m][k]) * Wp[n][k] + bias[n * bias_stride] )
+ * x_kind / y_kind (dlrm_linear16_kind) say what X and Y hold: DLRM_L16_FP32 = fp32 (X rounded
+ * in flight, as dlrm_linear16_forward does; Y the fp32 result), DLRM_L16_HALF = elements of
+ * `type` (X used as it is; Y = r16(y), one more nearest-even rounding of the fp32 result).
+ * ldx and ldy are in elements of their kind.  fp32 accumulation on
+ * v_mfma_f32_16x16x32_{bf16,f16}, fp32 bias (NULL: none) and ReLU (NaN propagates).
+ * Bit contract: with Wp = dlrm_linear16_pack(W) and the same DLRM_TUNE_LINEAR16_TILE the fp32
+ * result equals (==) dlrm_linear16_forward's on (X, W), a 16-bit X standing for the fp32
+ * tensor it was rounded from: the same tile plan, K in steps of 64 with two 32-k MFMA slices
+ * in the same order, the same operand-to-lane map.
+ * A 16-bit X needs K % 8 == 0, ldx % 8 == 0 and a 16-byte aligned X; a 16-bit Y ldy % 8 == 0
+ * and a 16-byte aligned Y (N may be any size); Wp as the packer requires; ldx >= K, ldy >= N
+ * (all DLRM_ERR_SHAPE).  An unknown type or kind or a NULL required pointer is
+ * DLRM_ERR_INVALID_ARG, more than 2^31 - 1 tiles DLRM_ERR_UNSUPPORTED.  Only Y[0:M][0:N] is
+ * written; no X[.][k >= K] and no row >= M / >= N is read (Wp's pad is read: it is zero).  An
+ * fp32 X takes 16-byte loads when it is 16-byte aligned and ldx a multiple of 4, element
+ * loads otherwise.  No split-K, no atomics, no workspace: two calls give the same bits.
+ * M == 0 or N == 0: nothing to do.
+ */
+enum dlrm_linear16_kind { DLRM_L16_FP32 = 0, DLRM_L16_HALF = 1 };
+int dlrm_linear16_pack(int32_t type, int64_t N, int64_t K, const float* W, int64_t ldw,
+                       void* Wp, int64_t ldwp, dlrm_stream_t stream);
+int dlrm_linear16_forward_packed(int32_t type, int64_t M, int64_t N, int64_t K, const void* X,
+                                 int32_t x_kind, int64_t ldx, const void* Wp, int64_t ldwp,
+                                 const float* bias, int64_t bias_stride, /* NULL: none */
+                                 int32_t relu, void* Y, int32_t y_kind, int64_t ldy,
+                                 dlrm_stream_t stream);
 
 /* ---------------------------------------------------- int8 inference Linear -- */
 /*

@@ -7,7 +7,8 @@
     commit is the yardstick; this one is for the ratio); with --precision fp32,bf16,fp16 one
     graph set per precision, timed in alternating windows (fp32, bf16, fp16, fp32, ...,
     --rounds of them) so the spread between the repeated fp32 windows - the unchanged
-    path - is the yardstick for the 16-bit ones;
+    path - is the yardstick for the 16-bit ones; "bf16+16" / "fp16+16" is that precision with
+    mlp_store=16 on a pack_mlp16 snapshot (16-bit weights and activations in memory);
   * metrics: dlrm_eval_metrics (sort + tie-group pass) on n random keys beside torch.sort of
     the same keys as int32.
 
@@ -40,6 +41,12 @@ def _time_ms(fn, steps, warmup):
     return evs[0].elapsed_time(evs[1]) / steps
 
 
+def _kw(p):
+    """"bf16" -> precision only; "bf16+16" -> that precision with mlp_store=16."""
+    prec, _, store = p.partition("+")
+    return dict(precision=prec, mlp_store=int(store)) if store else dict(precision=prec)
+
+
 def predict_timing(config, steps, warmup, dev, precisions=("fp32",), rounds=1):
     import bench
     from dlrm_hip import metrics
@@ -56,15 +63,21 @@ def predict_timing(config, steps, warmup, dev, precisions=("fp32",), rounds=1):
     tr = DLRMTrainer(cfg, device=dev, seed=1)
     nb = 10
     batches = [tr.synthetic_batch(B, c["L"], seed=100 + i) for i in range(nb)]
-    for b in batches[:3]:
-        tr.step(b)
-        for p in precisions:
-            tr.predict(b, precision=p)
+    for i, b in enumerate(batches):
+        if i < 3:
+            tr.step(b)
+        if i == 2:  # the snapshot of the weights every predict below reads
+            for p in precisions:
+                if "+" in p:
+                    tr.pack_mlp16(_kw(p)["precision"])
+        if i >= 2:
+            for p in precisions:
+                tr.predict(b, **_kw(p))
     torch.cuda.synchronize()
     st = metrics.EvalState((steps + warmup + 2 * nb) * B, dev)
     pool = torch.cuda.graph_pool_handle()
     train = [tr.capture(b, pool=pool) for b in batches]
-    preds = {p: [tr.capture_predict(b, metrics=st, pool=pool, precision=p) for b in batches]
+    preds = {p: [tr.capture_predict(b, metrics=st, pool=pool, **_kw(p)) for b in batches]
              for p in precisions}
     torch.cuda.synchronize()
     for g in train + [g for p in precisions for g in preds[p]]:  # first (upload) replays
