@@ -72,6 +72,23 @@ namespace {
                                               int32_t, int64_t, const void*, int64_t,
                                               const float*, int64_t, int32_t, void*, int32_t,
                                               int64_t, dlrm_stream_t) = &dlrm_linear16_forward_packed;
+[[maybe_unused]] int (*const kLinear16FwdFmt)(int32_t, int64_t, int64_t, int64_t, const void*,
+                                              int32_t, int64_t, const float*, int64_t,
+                                              const float*, int64_t, int32_t, void*, int32_t,
+                                              int64_t, dlrm_stream_t) = &dlrm_linear16_forward_fmt;
+[[maybe_unused]] int (*const kLinear16DgradFmt)(int32_t, int64_t, int64_t, int64_t, const void*,
+                                                int32_t, int64_t, const float*, int64_t,
+                                                const void*, int32_t, int64_t, void*, int32_t,
+                                                int64_t, dlrm_stream_t) = &dlrm_linear16_dgrad_fmt;
+[[maybe_unused]] int (*const kLinear16WgradFmt)(int32_t, int64_t, int64_t, int64_t, const void*,
+                                                int32_t, int64_t, const void*, int32_t, int64_t,
+                                                int32_t, float, float*, int64_t, void*, size_t,
+                                                dlrm_stream_t) = &dlrm_linear16_wgrad_fmt;
+[[maybe_unused]] int (*const kLinear16WgradFmtDev)(int32_t, int64_t, int64_t, int64_t,
+                                                   const void*, int32_t, int64_t, const void*,
+                                                   int32_t, int64_t, int32_t, const float*,
+                                                   float*, int64_t, void*, size_t,
+                                                   dlrm_stream_t) = &dlrm_linear16_wgrad_fmt_dev;
 }  // namespace
 
 extern "C" int dlrm_abi_version(void) { return DLRM_ABI_VERSION; }

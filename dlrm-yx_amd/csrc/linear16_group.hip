@@ -104,7 +104,7 @@ __device__ __forceinline__ void group_tile(const GroupProb& P, typename Op16<T>:
   bwd_tile_acc<T, BM, BN, TRANS_A, ALIGNED>(p, lds, orig, split, acc, i0, j0);
   // `orig` names the tile as well as its remapped index does: one ticket, one record run
   if (P.splits > 1 && !split_fold<BM, BN>(P, orig, split, acc, lds)) return;
-  bwd_tile_store<BM, BN>(p, p.epi, lr, acc, i0, j0, p.Out, p.ldo);
+  bwd_tile_store<BM, BN>(p, p.epi, lr, acc, i0, j0, static_cast<float*>(p.Out), p.ldo);
 }
 
 template <typename T, int BM, int BN>

@@ -4,6 +4,9 @@
 //   dlrm_linear16_forward_packed : Y = act(r16(X) Wp^T + bias); X fp32 (rounded in flight, as
 //                                  dlrm_linear16_forward does) or already 16-bit; Y fp32 or
 //                                  r16(y).
+//   dlrm_linear16_forward_fmt    : the same kernel on the fp32 W itself (rounded in flight by
+//                                  Stage<>, as dlrm_linear16_forward does) with a 16-bit X
+//                                  and / or Y: the training step's forward (store16).
 // The MFMA sees exactly the operand bits dlrm_linear16_forward feeds it - r16(W) was stored by
 // the packer, a 16-bit X is what the layer before stored as r16(y) - in the same tile, the
 // same k order (steps of 64, two 32-k slices each) and the same lane map, so the accumulators
@@ -61,40 +64,12 @@ __global__ __launch_bounds__(256) void pack16_kernel(int64_t N, int64_t K,
 }
 
 // ----------------------------------------------------------------- staging --
-// One thread's share of a [ROWS][64] 16-bit tile: chunk (tid & 7) of rows (tid >> 3) + 32 i,
-// each chunk 16 bytes from global memory to LDS as it is.
-template <typename T, int ROWS>
-struct Stage16 {
-  using vec = typename Op16<T>::vec;
-  static constexpr int kIter = ROWS / 32;
-  vec v[kIter];
+// (Stage16, the whole-chunk stager of a 16-bit tile, is linear16_stage.hpp's)
+// kPacked: dlrm_linear16_pack's image (every row readable and zero up to the k-step's end)
+enum XKind { kXF32Vec = 0, kXF32Elem = 1, kX16 = 2, kPacked = 3 };
 
-  // PADDED: every row is readable (and zero) up to the end of the k-step (Wp).  Otherwise
-  // K % 8 == 0 and a chunk lies wholly below K or wholly at k >= K, where it is not read.
-  template <bool PADDED>
-  __device__ __forceinline__ void load(const T* __restrict__ P, int64_t ld, int64_t row0,
-                                       int64_t rows, int64_t k0, int64_t K, int tid) {
-    const int64_t k = k0 + (tid & 7) * 8;
-#pragma unroll
-    for (int i = 0; i < kIter; ++i) {
-      int64_t r = row0 + (tid >> 3) + 32 * i;
-      r = r < rows ? r : rows - 1;  // clamped rows are computed but never written
-      if (PADDED || k < K)
-        v[i] = *reinterpret_cast<const vec*>(P + r * ld + k);
-      else
-        v[i] = vec{};  // selected, never multiplied by a value from memory
-    }
-  }
-
-  __device__ __forceinline__ void store(vec* lds, int tid) const {
-#pragma unroll
-    for (int i = 0; i < kIter; ++i) lds[lds_chunk((tid >> 3) + 32 * i, tid & 7)] = v[i];
-  }
-};
-
-enum XKind { kXF32Vec = 0, kXF32Elem = 1, kX16 = 2 };
-
-// The X tile's stager: fp32 in memory -> Stage<> (rounded while it is written to LDS) ...
+// The stager of an operand tile (X, or W as the second operand): fp32 in memory -> Stage<>
+// (rounded while it is written to LDS) ...
 template <typename T, int ROWS, int XK>
 struct XTile {
   Stage<ROWS> s;
@@ -122,12 +97,24 @@ struct XTile<T, ROWS, kX16> {
     s.store(lds, tid);
   }
 };
+// ... and the packer's image, which has no tail logic at all
+template <typename T, int ROWS>
+struct XTile<T, ROWS, kPacked> {
+  Stage16<T, ROWS> s;
+  __device__ __forceinline__ void load(const void* W, int64_t ld, int64_t n0, int64_t N,
+                                       int64_t k0, int64_t K, int tid) {
+    s.template load<true>(static_cast<const T*>(W), ld, n0, N, k0, K, tid);
+  }
+  __device__ __forceinline__ void store(typename Op16<T>::vec* lds, int tid) const {
+    s.store(lds, tid);
+  }
+};
 
 struct PackedArgs {
   int64_t M, N, K;
   const void* X;
   int64_t ldx;
-  const void* Wp;
+  const void* Wp;  // WK == kPacked: the 16-bit image; else the fp32 W of dlrm_linear16_forward_fmt
   int64_t ldwp;
   const float* bias;
   int64_t bias_stride;
@@ -136,7 +123,7 @@ struct PackedArgs {
   int64_t ldy;
 };
 
-template <typename T, int BM, int BN, int XK, bool Y16>
+template <typename T, int BM, int BN, int XK, int WK, bool Y16>
 __global__ __launch_bounds__(kThreads) void linear16_packed_kernel(PackedArgs a, int tiles_n,
                                                                    int tiles) {
   using vec = typename Op16<T>::vec;
@@ -167,12 +154,11 @@ __global__ __launch_bounds__(kThreads) void linear16_packed_kernel(PackedArgs a,
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   XTile<T, BM, XK> sa;
-  Stage16<T, BN> sb;
-  const T* Wp = static_cast<const T*>(a.Wp);
+  XTile<T, BN, WK> sb;
   const int64_t nk = (K + kBK - 1) / kBK;
   auto fetch = [&](int64_t kt) {
     sa.load(a.X, a.ldx, m0, M, kt * kBK, K, tid);
-    sb.template load<true>(Wp, a.ldwp, n0, N, kt * kBK, K, tid);
+    sb.load(a.Wp, a.ldwp, n0, N, kt * kBK, K, tid);
   };
   auto commit = [&](int buf) {
     sa.store(lds[buf], tid);
@@ -271,34 +257,52 @@ Tile plan_tile(int64_t M, int64_t N, int cus) {
   return kTiles[kNumTiles - 1];
 }
 
-template <typename T, int BM, int BN, int XK>
-void launch_y(bool y16, const PackedArgs& a, hipStream_t s) {
+template <typename T, int BM, int BN, int XK, int WK, bool Y16>
+void launch_one(const PackedArgs& a, hipStream_t s) {
   const int tiles_n = int(ceil_div(a.N, BN));
   const int tiles = int(ceil_div(a.M, BM)) * tiles_n;
-  if (y16)
-    hipLaunchKernelGGL((linear16_packed_kernel<T, BM, BN, XK, true>), dim3(tiles),
-                       dim3(kThreads), 0, s, a, tiles_n, tiles);
-  else
-    hipLaunchKernelGGL((linear16_packed_kernel<T, BM, BN, XK, false>), dim3(tiles),
-                       dim3(kThreads), 0, s, a, tiles_n, tiles);
+  hipLaunchKernelGGL((linear16_packed_kernel<T, BM, BN, XK, WK, Y16>), dim3(tiles),
+                     dim3(kThreads), 0, s, a, tiles_n, tiles);
 }
 
-template <typename T, int BM, int BN>
-void launch(int xk, bool y16, const PackedArgs& a, hipStream_t s) {
-  if (xk == kX16)
-    launch_y<T, BM, BN, kX16>(y16, a, s);
-  else if (xk == kXF32Vec)
-    launch_y<T, BM, BN, kXF32Vec>(y16, a, s);
+template <typename T, int BM, int BN, int XK, int WK>
+void launch_y(bool y16, const PackedArgs& a, hipStream_t s) {
+  if (y16)
+    launch_one<T, BM, BN, XK, WK, true>(a, s);
   else
-    launch_y<T, BM, BN, kXF32Elem>(y16, a, s);
+    launch_one<T, BM, BN, XK, WK, false>(a, s);
+}
+
+// wk == kPacked: dlrm_linear16_forward_packed's kernels.  Else dlrm_linear16_forward_fmt's: W
+// fp32 (wk says how it loads; an fp32 X loads the same way), and an fp32 X only beside a
+// 16-bit Y - fp32 X to fp32 Y is dlrm_linear16_forward's kernel and is not built here.
+template <typename T, int BM, int BN>
+void launch(int xk, int wk, bool y16, const PackedArgs& a, hipStream_t s) {
+  if (wk == kPacked) {
+    if (xk == kX16)
+      launch_y<T, BM, BN, kX16, kPacked>(y16, a, s);
+    else if (xk == kXF32Vec)
+      launch_y<T, BM, BN, kXF32Vec, kPacked>(y16, a, s);
+    else
+      launch_y<T, BM, BN, kXF32Elem, kPacked>(y16, a, s);
+  } else if (xk == kX16) {
+    if (wk == kXF32Vec)
+      launch_y<T, BM, BN, kX16, kXF32Vec>(y16, a, s);
+    else
+      launch_y<T, BM, BN, kX16, kXF32Elem>(y16, a, s);
+  } else if (wk == kXF32Vec) {
+    launch_one<T, BM, BN, kXF32Vec, kXF32Vec, true>(a, s);
+  } else {
+    launch_one<T, BM, BN, kXF32Elem, kXF32Elem, true>(a, s);
+  }
 }
 
 template <typename T>
-bool dispatch(Tile t, int xk, bool y16, const PackedArgs& a, hipStream_t s) {
-#define DLRM_L16P_CASE(BM, BN)         \
-  if (t.bm == BM && t.bn == BN) {      \
-    launch<T, BM, BN>(xk, y16, a, s);  \
-    return true;                       \
+bool dispatch(Tile t, int xk, int wk, bool y16, const PackedArgs& a, hipStream_t s) {
+#define DLRM_L16P_CASE(BM, BN)             \
+  if (t.bm == BM && t.bn == BN) {          \
+    launch<T, BM, BN>(xk, wk, y16, a, s);  \
+    return true;                           \
   }
   DLRM_L16P_CASE(128, 128)
   DLRM_L16P_CASE(128, 64)
@@ -307,8 +311,6 @@ bool dispatch(Tile t, int xk, bool y16, const PackedArgs& a, hipStream_t s) {
 #undef DLRM_L16P_CASE
   return false;
 }
-
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 }  // namespace dlrm
@@ -388,8 +390,65 @@ extern "C" int dlrm_linear16_forward_packed(int32_t type, int64_t M, int64_t N, 
                                                   : kXF32Elem;
   const PackedArgs a{M, N, K, X, ldx, Wp, ldwp, bias, bias_stride, relu, Y, ldy};
   const bool y16 = y_kind == DLRM_L16_HALF;
-  const bool ok = type == DLRM_MLP16_BF16 ? dispatch<__bf16>(t, xk, y16, a, as_stream(stream))
-                                          : dispatch<_Float16>(t, xk, y16, a, as_stream(stream));
+  const bool ok = type == DLRM_MLP16_BF16
+                      ? dispatch<__bf16>(t, xk, kPacked, y16, a, as_stream(stream))
+                      : dispatch<_Float16>(t, xk, kPacked, y16, a, as_stream(stream));
+  DLRM_REQUIRE(ok, DLRM_ERR_UNSUPPORTED, "%s: no kernel for the tile", fn);
+  DLRM_LAUNCH_CHECK(fn);
+  return DLRM_OK;
+}
+
+extern "C" int dlrm_linear16_forward_fmt(int32_t type, int64_t M, int64_t N, int64_t K,
+                                         const void* X, int32_t x_kind, int64_t ldx,
+                                         const float* W, int64_t ldw, const float* bias,
+                                         int64_t bias_stride, int32_t relu, void* Y,
+                                         int32_t y_kind, int64_t ldy, dlrm_stream_t stream) {
+  using namespace dlrm;
+  const char* fn = "dlrm_linear16_forward_fmt";
+  DLRM_ARG(type == DLRM_MLP16_BF16 || type == DLRM_MLP16_F16, "%s: unknown type %d", fn,
+           (int)type);
+  DLRM_ARG(x_kind == DLRM_L16_FP32 || x_kind == DLRM_L16_HALF, "%s: unknown x_kind %d", fn,
+           (int)x_kind);
+  DLRM_ARG(y_kind == DLRM_L16_FP32 || y_kind == DLRM_L16_HALF, "%s: unknown y_kind %d", fn,
+           (int)y_kind);
+  DLRM_ARG(M >= 0 && N >= 0 && K >= 0, "%s: negative size", fn);
+  DLRM_REQUIRE(x_kind == DLRM_L16_HALF || y_kind == DLRM_L16_HALF, DLRM_ERR_UNSUPPORTED,
+               "%s: fp32 X to fp32 Y is dlrm_linear16_forward", fn);
+  if (M == 0 || N == 0) return DLRM_OK;
+  DLRM_ARG(Y && (K == 0 || (X && W)), "%s: null pointer", fn);
+  DLRM_REQUIRE(ldx >= K && ldw >= K && ldy >= N, DLRM_ERR_SHAPE,
+               "%s: ldx %lld / ldw %lld < K %lld or ldy %lld < N %lld", fn, (long long)ldx,
+               (long long)ldw, (long long)K, (long long)ldy, (long long)N);
+  if (x_kind == DLRM_L16_HALF) {
+    DLRM_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && aligned16(X), DLRM_ERR_SHAPE,
+                 "%s: a 16-bit X needs K %lld and ldx %lld multiples of 8 and X 16-byte aligned",
+                 fn, (long long)K, (long long)ldx);
+  }
+  if (y_kind == DLRM_L16_HALF) {
+    DLRM_REQUIRE(N % 8 == 0 && ldy % 8 == 0 && aligned16(Y), DLRM_ERR_SHAPE,
+                 "%s: a 16-bit Y needs N %lld and ldy %lld multiples of 8 and Y 16-byte aligned",
+                 fn, (long long)N, (long long)ldy);
+  }
+  const int64_t forced = tuning(DLRM_TUNE_LINEAR16_TILE);
+  Tile t{int(forced / 1000), int(forced % 1000)};
+  if (forced != 0) {
+    DLRM_ARG(known_tile(t), "%s: DLRM_TUNE_LINEAR16_TILE %lld is not a tile", fn,
+             (long long)forced);
+  }
+  DLRM_REQUIRE(ceil_div(M, 32) * ceil_div(N, 64) <= INT32_MAX, DLRM_ERR_UNSUPPORTED,
+               "%s: more than 2^31 - 1 tiles", fn);
+  if (forced == 0) t = plan_tile(M, N, device_cus());
+  // the fp32 operands (W, and X where it is fp32) take 16-byte loads where each of them starts
+  // every row on a 16-byte boundary; elements at k >= K are not read on any path
+  const bool vec = aligned16(W) && ldw % 4 == 0 &&
+                   (x_kind == DLRM_L16_HALF || (aligned16(X) && ldx % 4 == 0));
+  const int wk = vec ? kXF32Vec : kXF32Elem;
+  const int xk = x_kind == DLRM_L16_HALF ? kX16 : wk;
+  const PackedArgs a{M, N, K, X, ldx, W, ldw, bias, bias_stride, relu, Y, ldy};
+  const bool y16 = y_kind == DLRM_L16_HALF;
+  const bool ok = type == DLRM_MLP16_BF16
+                      ? dispatch<__bf16>(t, xk, wk, y16, a, as_stream(stream))
+                      : dispatch<_Float16>(t, xk, wk, y16, a, as_stream(stream));
   DLRM_REQUIRE(ok, DLRM_ERR_UNSUPPORTED, "%s: no kernel for the tile", fn);
   DLRM_LAUNCH_CHECK(fn);
   return DLRM_OK;

@@ -79,6 +79,40 @@ struct Stage {
   }
 };
 
+// One thread's share of a [ROWS][64] 16-bit tile: chunk (tid & 7) of rows (tid >> 3) + 32 i,
+// each chunk 16 bytes from global memory to LDS as it is.
+template <typename T, int ROWS>
+struct Stage16 {
+  using vec = typename Op16<T>::vec;
+  static constexpr int kIter = ROWS / 32;
+  vec v[kIter];
+
+  // PADDED: every row is readable (and zero) up to the end of the k-step (Wp).  Otherwise
+  // K % 8 == 0 and a chunk lies wholly below K or wholly at k >= K, where it is not read.
+  template <bool PADDED>
+  __device__ __forceinline__ void load(const T* __restrict__ P, int64_t ld, int64_t row0,
+                                       int64_t rows, int64_t k0, int64_t K, int tid) {
+    const int64_t k = k0 + (tid & 7) * 8;
+#pragma unroll
+    for (int i = 0; i < kIter; ++i) {
+      int64_t r = row0 + (tid >> 3) + 32 * i;
+      r = r < rows ? r : rows - 1;  // clamped rows are computed but never written
+      if (PADDED || k < K)
+        v[i] = *reinterpret_cast<const vec*>(P + r * ld + k);
+      else
+        v[i] = vec{};  // selected, never multiplied by a value from memory
+    }
+  }
+
+  __device__ __forceinline__ void store(vec* lds, int tid) const {
+#pragma unroll
+    for (int i = 0; i < kIter; ++i) lds[lds_chunk((tid >> 3) + 32 * i, tid & 7)] = v[i];
+  }
+};
+
+// the base of a 16-bit operand, which moves as whole 16-byte chunks
+inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
 struct Tile {
   int bm, bn;
 };

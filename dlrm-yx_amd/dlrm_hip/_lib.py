@@ -273,6 +273,20 @@ SIGNATURES = {
     "dlrm_linear16_forward_packed": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
                                                c_int64, P, c_int64, P, c_int64, c_int32, P,
                                                c_int32, c_int64, P]),
+    # added to ABI v23 likewise: the training step's Linear kernels with a memory format per
+    # activation / gradient operand (fp32 or the launch's 16-bit type)
+    "dlrm_linear16_forward_fmt": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
+                                            c_int64, P, c_int64, P, c_int64, c_int32, P, c_int32,
+                                            c_int64, P]),
+    "dlrm_linear16_dgrad_fmt": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
+                                          c_int64, P, c_int64, P, c_int32, c_int64, P, c_int32,
+                                          c_int64, P]),
+    "dlrm_linear16_wgrad_fmt": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
+                                          c_int64, P, c_int32, c_int64, c_int32, c_float, P,
+                                          c_int64, P, c_size_t, P]),
+    "dlrm_linear16_wgrad_fmt_dev": (c_int32, [c_int32, c_int64, c_int64, c_int64, P, c_int32,
+                                              c_int64, P, c_int32, c_int64, c_int32, P, P,
+                                              c_int64, P, c_size_t, P]),
 }
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "SHAPE", 3: "UNSUPPORTED", 4: "WORKSPACE", 5: "HIP"}

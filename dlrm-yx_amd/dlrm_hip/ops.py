@@ -1042,9 +1042,25 @@ def _row_major(t: torch.Tensor, what: str, fn: str = "linear16_forward") -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], 1)
 
 
+def _want16(out: Optional[torch.Tensor], out_dtype, dtype: str, fn: str) -> bool:
+    """Whether the output of ``fn`` is to be the 16-bit ``dtype`` (else fp32)."""
+    if out is not None and out_dtype is not None and out.dtype != out_dtype:
+        raise ValueError(f"{fn}: out is {out.dtype}, out_dtype {out_dtype}")
+    want = out.dtype if out is not None else (out_dtype or torch.float32)
+    if want not in (torch.float32, TORCH16[dtype]):
+        raise ValueError(f"{fn}: the output must be fp32 or {dtype}, not {want}")
+    return want != torch.float32
+
+
+def _empty16(M: int, N: int, dtype: str, device) -> torch.Tensor:
+    """An [M, N] 16-bit output whose rows start on 16-byte boundaries."""
+    return torch.empty((M, (N + 7) // 8 * 8), dtype=TORCH16[dtype], device=device)[:, :N]
+
+
 def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
                      relu: bool = False, out: Optional[torch.Tensor] = None,
-                     dtype: str = "bf16") -> torch.Tensor:
+                     dtype: str = "bf16",
+                     out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """Forward-only Linear on the 16-bit MFMA (dlrm_linear16_forward): out [M, N] =
     act(r16(x) r16(W)^T + bias), x [M, K] and W [N, K] fp32 tensors or views with contiguous
     rows, each element rounded to nearest-even ``dtype`` ("bf16" | "fp16") in flight, fp32
@@ -1052,10 +1068,16 @@ def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tens
     W's buffer).  Only out[:M, :N] is written (``out`` may be a view of a wider buffer).
     The library takes 16-byte loads when both base addresses (storage offset included) are
     16-byte aligned and both row strides are multiples of 4, scalar loads otherwise; neither
-    reads past column K of any row, so the extent of the last row never matters."""
+    reads past column K of any row, so the extent of the last row never matters.
+    ``x`` may instead be a tensor of ``dtype`` (torch.bfloat16 / torch.float16: used as it is),
+    and ``out`` / ``out_dtype`` may ask for one (r16 of the fp32 result): 16-byte aligned, row
+    stride and width multiples of 8.  Such a call is dlrm_linear16_forward_fmt; its fp32
+    output is bit for bit this function's on the widened x, a 16-bit one that cast once."""
     if dtype not in MLP16_TYPES:
         raise ValueError(f"linear16_forward: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
     _check_cuda(x, W, bias, out)
+    if x.dtype != torch.float32 or _want16(out, out_dtype, dtype, "linear16_forward"):
+        return _linear16_forward_fmt(x, W, bias, relu, out, dtype, out_dtype)
     ldx, ldw = _row_major(x, "x"), _row_major(W, "W")
     (M, K), N = x.shape, W.shape[0]
     if W.shape[1] != K:
@@ -1072,6 +1094,30 @@ def linear16_forward(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tens
         bstride = bias.stride(0) if N > 1 else 1
     _lib.call("dlrm_linear16_forward", MLP16_TYPES[dtype], M, N, K, _p(x), ldx, _p(W), ldw,
               _p(bias), bstride, int(bool(relu)), _p(out), ldy, _stream(x.device))
+    return out
+
+
+def _linear16_forward_fmt(x, W, bias, relu, out, dtype, out_dtype):
+    fn = "linear16_forward"
+    x_kind, ldx = _row_major16(x, dtype, "x", fn)
+    ldw = _row_major(W, "W")
+    (M, K), N = x.shape, W.shape[0]
+    if W.shape[1] != K:
+        raise ValueError(f"{fn}: x is [{M}, {K}], W is {list(W.shape)}")
+    if out is None:
+        out = _empty16(M, N, dtype, x.device) if _want16(out, out_dtype, dtype, fn) \
+            else torch.empty((M, N), dtype=torch.float32, device=x.device)
+    if out.dim() != 2 or tuple(out.shape) != (M, N):
+        raise ValueError(f"{fn}: out is {list(out.shape)}, expected [{M}, {N}]")
+    y_kind, ldy = _row_major16(out, dtype, "out", fn)
+    bstride = 0
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != N or bias.dtype != torch.float32:
+            raise ValueError(f"{fn}: bias must be N fp32 values")
+        bstride = bias.stride(0) if N > 1 else 1
+    _lib.call("dlrm_linear16_forward_fmt", MLP16_TYPES[dtype], M, N, K, _p(x), x_kind, ldx,
+              _p(W), ldw, _p(bias), bstride, int(bool(relu)), _p(out), y_kind, ldy,
+              _stream(x.device))
     return out
 
 
@@ -1348,15 +1394,22 @@ WGRAD16_STORE, WGRAD16_SGD = 0, 1  # dlrm_wgrad16_mode
 
 
 def linear16_dgrad(g: torch.Tensor, W: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                   out: Optional[torch.Tensor] = None, dtype: str = "bf16") -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, dtype: str = "bf16",
+                   out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """A Linear's data gradient on the 16-bit MFMA (dlrm_linear16_dgrad): out [M, K] =
     r16(g) r16(W) where ``mask`` > 0 (mask None: everywhere), 0 elsewhere; g [M, N], W [N, K],
     mask [M, K] fp32 tensors or views with contiguous rows, rounded to nearest-even ``dtype``
     in flight, fp32 accumulate.  Only out[:M, :K] is written.  Enqueues only; allocates
-    nothing when ``out`` is given."""
+    nothing when ``out`` is given.  ``g`` may instead be a tensor of ``dtype`` (used as it
+    is) and ``out`` / ``out_dtype`` may ask for one (r16 of the fp32 result; ``mask`` is then of
+    ``dtype`` too and tested as stored): 16-byte aligned, row stride and width multiples of
+    8 (dlrm_linear16_dgrad_fmt; the bits of this function on the widened operands)."""
     if dtype not in MLP16_TYPES:
         raise ValueError(f"linear16_dgrad: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
     _check_cuda(g, W, mask, out)
+    if g.dtype != torch.float32 or (mask is not None and mask.dtype != torch.float32) \
+            or _want16(out, out_dtype, dtype, "linear16_dgrad"):
+        return _linear16_dgrad_fmt(g, W, mask, out, dtype, out_dtype)
     ldg, ldw = _row_major(g, "g", "linear16_dgrad"), _row_major(W, "W", "linear16_dgrad")
     (M, N), K = g.shape, W.shape[1]
     if W.shape[0] != N:
@@ -1376,6 +1429,29 @@ def linear16_dgrad(g: torch.Tensor, W: torch.Tensor, mask: Optional[torch.Tensor
     return out
 
 
+def _linear16_dgrad_fmt(g, W, mask, out, dtype, out_dtype):
+    fn = "linear16_dgrad"
+    g_kind, ldg = _row_major16(g, dtype, "g", fn)
+    ldw = _row_major(W, "W", fn)
+    (M, N), K = g.shape, W.shape[1]
+    if W.shape[0] != N:
+        raise ValueError(f"{fn}: g is [{M}, {N}], W is {list(W.shape)}")
+    m_kind, ldm = L16_FP32, 0
+    if mask is not None:
+        m_kind, ldm = _row_major16(mask, dtype, "mask", fn)
+        if tuple(mask.shape) != (M, K):
+            raise ValueError(f"{fn}: mask is {list(mask.shape)}, expected [{M}, {K}]")
+    if out is None:
+        out = _empty16(M, K, dtype, g.device) if _want16(out, out_dtype, dtype, fn) \
+            else torch.empty((M, K), dtype=torch.float32, device=g.device)
+    if out.dim() != 2 or tuple(out.shape) != (M, K):
+        raise ValueError(f"{fn}: out is {list(out.shape)}, expected [{M}, {K}]")
+    o_kind, ldo = _row_major16(out, dtype, "out", fn)
+    _lib.call("dlrm_linear16_dgrad_fmt", MLP16_TYPES[dtype], M, N, K, _p(g), g_kind, ldg, _p(W),
+              ldw, _p(mask), m_kind, ldm, _p(out), o_kind, ldo, _stream(g.device))
+    return out
+
+
 def linear16_wgrad_workspace_size(M: int, N: int, K: int, dtype: str = "bf16") -> int:
     """Bytes of workspace linear16_wgrad needs for these sizes under the calling thread's
     tuning overrides (0: none)."""
@@ -1390,11 +1466,19 @@ def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     ``dtype`` in flight, fp32 accumulate.  ``lr`` None: out = acc; else (a float or a
     1-element fp32 device tensor) the fused SGD step out = out - fl(lr * acc).  Only out[:N, :K] is touched.  ``workspace`` (any contiguous
     tensor of at least linear16_wgrad_workspace_size bytes) holds the partial sums when the
-    planner splits the batch; it is allocated here when needed and not given.  Enqueues only."""
+    planner splits the batch; it is allocated here when needed and not given.  Enqueues only.
+    ``g`` and ``x`` may each instead be a tensor of ``dtype`` (used as it is; 16-byte aligned,
+    row stride a multiple of 8, any width): dlrm_linear16_wgrad_fmt, the bits of this function
+    on the widened operands, the same workspace."""
     if dtype not in MLP16_TYPES:
         raise ValueError(f"linear16_wgrad: dtype {dtype!r} (one of {sorted(MLP16_TYPES)})")
     _check_cuda(g, x, out, workspace)
-    ldg, ldx = _row_major(g, "g", "linear16_wgrad"), _row_major(x, "x", "linear16_wgrad")
+    fmt = g.dtype != torch.float32 or x.dtype != torch.float32
+    if fmt:
+        (g_kind, ldg), (x_kind, ldx) = (_row_major16(g, dtype, "g", "linear16_wgrad"),
+                                        _row_major16(x, dtype, "x", "linear16_wgrad"))
+    else:
+        ldg, ldx = _row_major(g, "g", "linear16_wgrad"), _row_major(x, "x", "linear16_wgrad")
     (M, N), K = g.shape, x.shape[1]
     if x.shape[0] != M:
         raise ValueError(f"linear16_wgrad: g is [{M}, {N}], x is {list(x.shape)}")
@@ -1411,6 +1495,16 @@ def linear16_wgrad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor,
     if ws_bytes < need:
         raise ValueError(f"linear16_wgrad: workspace of {ws_bytes} bytes, {need} needed")
     lr_dev = _lr_dev(lr, "linear16_wgrad: lr")
+    if fmt:
+        head = (MLP16_TYPES[dtype], M, N, K, _p(g), g_kind, ldg, _p(x), x_kind, ldx)
+        tail = (_p(out), ldc, _p(workspace), ws_bytes, _stream(g.device))
+        if lr_dev is not None:
+            _lib.call("dlrm_linear16_wgrad_fmt_dev", *head, WGRAD16_SGD, lr_dev, *tail)
+        else:
+            _lib.call("dlrm_linear16_wgrad_fmt", *head,
+                      WGRAD16_STORE if lr is None else WGRAD16_SGD,
+                      0.0 if lr is None else float(lr), *tail)
+        return out
     if lr_dev is not None:
         _lib.call("dlrm_linear16_wgrad_dev", MLP16_TYPES[dtype], M, N, K, _p(g), ldg, _p(x),
                   ldx, WGRAD16_SGD, lr_dev, _p(out), ldc, _p(workspace), ws_bytes,

@@ -482,6 +482,13 @@ class DLRMTrainer:
         # default
         self.group_bwd16 = False
         self.bwd16_grouped = False  # set by the last build of a training step
+        # the bf16 training step with 16-bit activations and data gradients IN MEMORY (DESIGN.md
+        # §28): below the head, every buffer between two Linear layers of one MLP whose width
+        # is a multiple of 8 is a bf16 one, read and written as 16-byte chunks by the
+        # per-operand-format kernels (ops.linear16_forward / _dgrad / _wgrad on 16-bit
+        # tensors) - the operand bits of the fp32-buffer step, so the same weights and loss.
+        # One GPU, per-layer launches (not with group_bwd16 or fuse_bottom16).  Off by default
+        self.store16 = False
         # device TBE error bits (ops.TBE_ERR_*): out-of-range indices are skipped by the
         # kernels and flagged here; check_errors() reads it (the step never syncs)
         self.tbe_error_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -1027,6 +1034,9 @@ class DLRMTrainer:
         chain16 = self._bottom_chain16(batch, bufs, precision, keep=train) \
             if self.fuse_bottom16 and not fp32 and q8 is None and p16 is None else None
         self.bottom16_fused = chain16 is not None
+        # store16: id(fp32 activation buffer) -> its 16-bit twin, and the 16-bit gradient
+        # rotations beside bufs["g"] / bufs["gb"]; empty when the mode is off
+        half, G16, gb16 = self._store16(bufs, precision) if train else ({}, None, None)
 
         if fp32:
             def mlp_fwd(L, h, out, side=False):
@@ -1059,11 +1069,14 @@ class DLRMTrainer:
         else:
             # 16 bit: one launch, relu(r16(h[:, :K]) r16(W[:, :K])^T + b) -> out[:, :N], the
             # operands rounded to nearest-even in flight from the fp32 tensors (no weight
-            # copy exists), fp32 accumulate; the constant-1 columns stay untouched
+            # copy exists), fp32 accumulate; the constant-1 columns stay untouched.
+            # store16 (training): a buffer with a 16-bit twin (_store16) is read and written
+            # there instead - r16(y), the bits the next launch would round it to
             def mlp_fwd(L, h, out, side=False):
                 with prof("gemm"):
-                    ops.linear16_forward(h[:, :L.K], L.W[:, :L.K], L.b, relu=True,
-                                         out=out[:, :L.N], dtype=precision)
+                    ops.linear16_forward(half.get(id(h), h)[:, :L.K], L.W[:, :L.K], L.b,
+                                         relu=True, out=half.get(id(out), out)[:, :L.N],
+                                         dtype=precision)
 
         # the reference's profiler phase names (dlrm_s_pytorch.py:692-721, 171, 1923), so a
         # torch.profiler trace of this step lines up with one of the reference's
@@ -1409,16 +1422,23 @@ class DLRMTrainer:
             # db = sum_m r16(g)), SGD-fused into W on one GPU with SGD, else stored into the
             # gradient bucket.  Stream order puts a layer's update after the dgrad that
             # reads its W.  group_wgrad, full_last_wgrad and bot_sched have no effect here.
+            # store16: an input activation with a 16-bit twin is read there (the mask as stored,
+            # [inp | 1] with the 1 in the twin's pad), and the gradient of such an activation is
+            # a 16-bit buffer too (gout); g is whichever buffer the layer above wrote.
+            def gout(inp, g32, g16):
+                return g16 if inp is not None and id(inp) in half else g32
+
             def dgrad16(L, g, inp, out):
                 with prof("gemm"):
                     ops.linear16_dgrad(g[:, :L.N], L.W[:, :L.K],
-                                       None if inp is None else inp[:, :L.K], out=out[:, :L.K],
-                                       dtype=precision)
+                                       None if inp is None else half.get(id(inp), inp)[:, :L.K],
+                                       out=out[:, :L.K], dtype=precision)
 
             def wgrad16(L, g, inp):
                 C = L.W if fused_opt else L.gW
                 with prof("gemm"):
-                    ops.linear16_wgrad(g[:, :L.N], inp[:, :L.K + 1], C[:, :L.K + 1],
+                    ops.linear16_wgrad(g[:, :L.N], half.get(id(inp), inp)[:, :L.K + 1],
+                                       C[:, :L.K + 1],
                                        lr=lr if fused_opt else None, dtype=precision,
                                        workspace=self._ws_wgrad16(bufs, Bl, L.N, L.K + 1))
 
@@ -1456,10 +1476,13 @@ class DLRMTrainer:
                     if grouped:
                         group16([dprob(L, g, inp if li > 0 else None, G[gn])] + pending)
                         pending = [wprob(L, g, inp)]
+                        g = G[gn]
                     else:
-                        dgrad16(L, g, inp if li > 0 else None, G[gn])
+                        out = gout(inp if li > 0 else None, G[gn], G16 and G16[gn])
+                        dgrad16(L, g, inp if li > 0 else None, out)
                         wgrad16(L, g, inp)
-                    g, gi = G[gn], gn
+                        g = out
+                    gi = gn
                 if pending:
                     group16(pending)
                 return g
@@ -1482,10 +1505,11 @@ class DLRMTrainer:
                             group16(pending + [w])
                         continue
                     if li > 0:
-                        dgrad16(L, g, inp, bufs["gb"][li % 2])
+                        out = gout(inp, bufs["gb"][li % 2], gb16 and gb16[li % 2])
+                        dgrad16(L, g, inp, out)
                     wgrad16(L, g, inp)
                     if li > 0:
-                        g = bufs["gb"][li % 2]
+                        g = out
 
         def top():  # interaction, top MLP, head, top backward
             x, feats = interaction_fwd()
@@ -1717,6 +1741,43 @@ class DLRMTrainer:
                                    "(the wgrad workspace)")
             ws = bufs["wgrad16_ws"] = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return ws
+
+    def _store16(self, bufs, precision: str):
+        """store16: (twins, G16, gb16) for this batch size, allocated once and
+        outside any capture - ``twins`` maps id(fp32 activation buffer) to its 16-bit twin,
+        one per output of a Linear that feeds the next Linear of the same MLP and whose width
+        N is a multiple of 8 (else that boundary stays fp32): [Bl, N + 8] with the constant-1
+        bias column at N, inside the pad that keeps the row stride a multiple of 8.  G16 / gb16
+        stand beside the gradient rotations bufs["g"] / bufs["gb"].  Off: ({}, None, None)."""
+        if not self.store16:
+            return {}, None, None
+        if precision == "fp32":
+            raise ValueError("store16 keeps the 16-bit MLP operands of mlp_precision='bf16' in "
+                             "memory; with fp32 MLPs there are none")
+        for flag, what in ((self.distributed, "world_size > 1"),
+                           (self.group_bwd16, "group_bwd16"),
+                           (self.fuse_bottom16, "fuse_bottom16")):
+            if flag:
+                raise NotImplementedError(f"store16 with {what}: the 16-bit buffers are wired "
+                                          "into the per-layer launches of one GPU only "
+                                          "(DESIGN.md §9)")
+        if "store16" not in bufs:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capture() needs one eager step of this batch size first "
+                                   "(the store16 buffers)")
+            h16 = dict(dtype=ops.TORCH16[precision], device=self.dev)
+            twins = {}
+            for layers, outs in ((self.bot, bufs["bot_act"]), (self.top[:-1], bufs["top_act"])):
+                for L, out in list(zip(layers, outs))[:-1]:
+                    if L.N % 8 == 0:
+                        t = twins[id(out)] = torch.zeros((out.shape[0], L.N + 8), **h16)
+                        t[:, L.N] = 1.0
+            bufs["store16"] = (twins,
+                               [torch.zeros((g.shape[0], (g.shape[1] + 7) // 8 * 8), **h16)
+                                for g in bufs["g"]],
+                               [torch.zeros((g.shape[0], (g.shape[1] + 7) // 8 * 8), **h16)
+                                for g in bufs["gb"][:2]])
+        return bufs["store16"]
 
     def _ws_group16(self, bufs, probs) -> Optional[torch.Tensor]:
         """The batch size's linear16_bwd_group workspace (tickets + split records; its launches

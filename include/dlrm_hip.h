@@ -1061,6 +1061,52 @@ int dlrm_linear16_forward_packed(int32_t type, int64_t M, int64_t N, int64_t K, 
                                  int32_t relu, void* Y, int32_t y_kind, int64_t ldy,
                                  dlrm_stream_t stream);
 
+/*
+ * The training step's Linear kernels with a memory format PER OPERAND (added to ABI v23):
+ * siblings of dlrm_linear16_forward / _dgrad / _wgrad / _wgrad_dev whose activation and
+ * gradient operands are fp32 (DLRM_L16_FP32: rounded in flight, as there) or already elements
+ * of `type` (DLRM_L16_HALF: used as they are, moved as 16-byte chunks with no conversion; an
+ * output is stored as r16 of the fp32 result).  W and C are always fp32.  Leading dimensions
+ * count elements of the operand's own format.
+ *
+ * Bit contract: an operand's 16-bit image stands for the fp32 tensor it was rounded from -
+ * under the same tuning overrides an fp32 output equals (==) the fp32 sibling's on the widened
+ * operands, a 16-bit output equals that result cast once (the same tile plans, reduction
+ * order and operand-to-lane map; a 16-bit mask is tested as stored: `mask > 0`, NaN gives 0).
+ *
+ * A 16-bit operand needs a 16-byte aligned base and a leading dimension that is a multiple of
+ * 8; its extent along the contiguous index must be a multiple of 8 where it is an output (Y:
+ * N, dX: K) or the reduction (forward X: K, dgrad dY: N); in wgrad, where the contiguous index
+ * is an output column, any extent is allowed and the chunk that crosses it is read by element
+ * (so X may be [inp | 1] with the constant-1 bias column inside the pad to a multiple of 8).
+ * Else DLRM_ERR_SHAPE.  Nothing outside the stated extents is read or written.
+ *
+ * Built combinations, every other one is DLRM_ERR_UNSUPPORTED before any launch:
+ *   forward (X, Y):  16/16, 16/fp32, fp32/16
+ *   dgrad (dY, dX):  16/16, 16/fp32, fp32/16; the mask (NULL: none) is of dX's format
+ *   wgrad (dY, X):   16/16, 16/fp32, fp32/16
+ * (all fp32 is the fp32 sibling's job).  dlrm_linear16_wgrad_workspace_size holds for
+ * dlrm_linear16_wgrad_fmt as it is: the plan does not depend on the formats.
+ */
+int dlrm_linear16_forward_fmt(int32_t type, int64_t M, int64_t N, int64_t K, const void* X,
+                              int32_t x_kind, int64_t ldx, const float* W, int64_t ldw,
+                              const float* bias, int64_t bias_stride, /* NULL: none */
+                              int32_t relu, void* Y, int32_t y_kind, int64_t ldy,
+                              dlrm_stream_t stream);
+int dlrm_linear16_dgrad_fmt(int32_t type, int64_t M, int64_t N, int64_t K, const void* dY,
+                            int32_t dy_kind, int64_t lddy, const float* W, int64_t ldw,
+                            const void* mask, int32_t mask_kind, int64_t ldmask, /* NULL: none */
+                            void* dX, int32_t dx_kind, int64_t lddx, dlrm_stream_t stream);
+int dlrm_linear16_wgrad_fmt(int32_t type, int64_t M, int64_t N, int64_t K, const void* dY,
+                            int32_t dy_kind, int64_t lddy, const void* X, int32_t x_kind,
+                            int64_t ldx, int32_t mode, float lr, float* C, int64_t ldc,
+                            void* workspace, size_t workspace_bytes, dlrm_stream_t stream);
+int dlrm_linear16_wgrad_fmt_dev(int32_t type, int64_t M, int64_t N, int64_t K, const void* dY,
+                                int32_t dy_kind, int64_t lddy, const void* X, int32_t x_kind,
+                                int64_t ldx, int32_t mode, const float* lr_dev, float* C,
+                                int64_t ldc, void* workspace, size_t workspace_bytes,
+                                dlrm_stream_t stream);
+
 /* ---------------------------------------------------- int8 inference Linear -- */
 /*
  * Forward-only Linear with int8 operands, dynamically quantized (ABI v18): the arithmetic of

@@ -63,16 +63,19 @@ def _trainer(config, dev, precision):
     return c, DLRMTrainer(cfg, device=dev, seed=1)
 
 
-def step_timing(config, steps, warmup, rounds, dev, group16=False):
+def step_timing(config, steps, warmup, rounds, dev, group16=False, store16=False):
     import bench
     # --group16: a third trainer, the bf16 step with DLRMTrainer.group_bwd16 on
-    modes = ("fp32", "bf16") + (("bf16_group",) if group16 else ())
+    # --store16: one more, the bf16 step with DLRMTrainer.store16 on (16-bit buffers in memory)
+    modes = ("fp32", "bf16") + (("bf16_group",) if group16 else ()) + \
+        (("bf16_store16",) if store16 else ())
     runs = {}
     nb = 10
     pool = torch.cuda.graph_pool_handle()
     for mode in modes:
         c, tr = _trainer(config, dev, mode.split("_")[0])
         tr.group_bwd16 = mode == "bf16_group"
+        tr.store16 = mode == "bf16_store16"
         batches = [tr.synthetic_batch(c["B"], c["L"], seed=100 + i) for i in range(nb)]
         for b in batches[:3]:
             tr.step(b)
@@ -107,6 +110,11 @@ def step_timing(config, steps, warmup, rounds, dev, group16=False):
         res["group_over_bf16"] = round(b["median"] / a["median"], 4)
         # a difference counts only beyond the spread between a mode's own windows
         res["group_differs"] = bool(abs(a["median"] - b["median"]) > max(a["spread"], b["spread"]))
+    if store16:
+        a, b = res["ms_per_step"]["bf16"], res["ms_per_step"]["bf16_store16"]
+        res["store16_over_bf16"] = round(b["median"] / a["median"], 4)
+        # faster only when the gap exceeds BOTH modes' window spreads
+        res["store16_faster"] = bool(a["median"] - b["median"] > max(a["spread"], b["spread"]))
     return res
 
 
@@ -189,6 +197,8 @@ def main():
     ap.add_argument("--skip-layers", action="store_true")
     ap.add_argument("--group16", action="store_true",
                     help="time the bf16 step with group_bwd16 on beside the other two")
+    ap.add_argument("--store16", action="store_true",
+                    help="time the bf16 step with store16 on beside the others")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train16_bench.json"))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -199,7 +209,7 @@ def main():
         torch.cuda.empty_cache()
     if not args.skip_step:
         res["step"] = step_timing(args.config, args.steps, args.warmup, args.rounds, dev,
-                                  args.group16)
+                                  args.group16, args.store16)
     text = json.dumps(res, indent=1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
